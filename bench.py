@@ -11,9 +11,12 @@ Multi-GPU: one process per GPU (torchrun); frames are independent, so each
 rank runs its own batch with no data-path collective (weak scaling); the
 barrier and the max-over-ranks of the timed region use torch.distributed.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
-`roofline` (algorithmic bytes / average kernel duration from HIP events on the
-launch stream, against the 8 TB/s HBM peak), `cpu_baseline` (the reference's
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps
+and prints it: the contract fields and `roofline` (algorithmic bytes / average
+kernel duration from HIP events on the launch stream, against the 8 TB/s HBM
+peak).  --dump-outputs DIR also writes the last timed step's levels there.
+Everything that takes runs of its own waits for --full: the oracle spot check,
+the measured ceiling and PMC traffic inside `roofline`, `cpu_baseline` (the reference's
 own downsampler.cpp, compiled unmodified into oracle/_ref, on one core over a
 bounded sample on this host, with the oracle port timed beside it), and `e2e` (host frame -> pinned H2D -> kernels -> D2H -> take_frame
 through the streaming API, the path's real end-to-end rate).
@@ -294,8 +297,51 @@ def parse(argv=None):
     p.add_argument("--per-launch-events", action="store_true",
                    help="an event pair around every launch (per-launch min; adds a "
                         "~12 us gap between kernels)")
+    p.add_argument("--full", action="store_true",
+                   help="besides the timed steps, run everything else the line can carry: "
+                        "the oracle spot check, the one-buffer-set contrast, the measured "
+                        "HBM ceiling, the PMC traffic passes, the CPU baseline and the "
+                        "end-to-end legs (--no-check, --no-pmc, --cpu-seconds, --e2e-frames "
+                        "and --sink trim these); without it a run sets up, warms up, times "
+                        "the steps and prints the line, with those fields null")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write the levels the last timed step "
+                        "produced to DIR/level_<L>.npy (--tiled: also the chunk flags, "
+                        "level_<L>_nonzero.npy), as float32 (float64 for 4- and 8-byte "
+                        "elements), at most 64 MB in all: a level too large for its share "
+                        "is a fixed, seeded sample of its elements")
     p.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     return p.parse_args(argv)
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # of .npy payload, under the 64 MB a dump may take
+
+
+def dump_outputs(dirname, arrays):
+    """Write `arrays` = [(name, 1-D device tensor of raw bytes, numpy dtype)]
+    to dirname/<name>.npy as float32 (float64 where the elements are wider
+    than 24 bits of integer or are doubles).  DUMP_BUDGET_BYTES is dealt from
+    the smallest array up: one that fits its share goes whole, a larger one
+    as the elements at a sorted index sample drawn from a generator seeded
+    by its place in the list and its length alone, so two runs with the same
+    arguments sample the same elements."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    order = sorted(range(len(arrays)), key=lambda i: arrays[i][1].numel())
+    for pos, i in enumerate(order):
+        name, raw, dtype = arrays[i]
+        dtype = np.dtype(dtype)
+        out_dtype = np.float32 if dtype.itemsize <= 2 or dtype == np.float32 else np.float64
+        n = raw.numel() // dtype.itemsize
+        share = left // (len(order) - pos) // np.dtype(out_dtype).itemsize
+        rows = raw.view(n, dtype.itemsize)
+        if n > share:
+            idx = np.sort(np.random.default_rng([0xD0, i, n]).integers(0, n, share))
+            rows = rows.index_select(0, torch.from_numpy(idx).to(raw.device))
+        host = rows.cpu().numpy().reshape(-1).view(dtype).astype(out_dtype)
+        left -= host.nbytes
+        np.save(os.path.join(dirname, name + ".npy"), host)
 
 
 def main():
@@ -496,11 +542,12 @@ def main():
 
     # correctness spot check of one frame against the oracle (rank 0, N=1)
     check = None
-    if not args.no_check:
+    do_check = args.full and not args.no_check
+    if do_check:
         turn[0] = 0  # the checked outputs are copy 0's
         step()  # every rank: in --xgmi-scatter mode the step is collective
         torch.cuda.synchronize()
-    if not args.no_check and rank == 0:
+    if do_check and rank == 0:
         import oracle as orc_mod  # test infrastructure: checker only
         # first 2^(levels-1) frames (one aligned plane group for volumes)
         nchk = min(B, 1 << (n_levels - 1)) if Z else 1
@@ -565,6 +612,23 @@ def main():
             evs[0][2].record(stream)
 
     elapsed = timed_region(timed_step, args.steps, dist, torch.cuda.synchronize)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step wrote: the node's or rank 0's gathered
+        # levels, else the output set of the buffer copy that step ran on
+        k = (turn[0] - 1) % n_rot
+        if xnode is not None:
+            last, last_flags = xnode["levels"], None
+        elif xgmi:
+            last, last_flags = pool_levels, None
+        else:
+            last = outs if k == 0 else rot_outs[k - 1]
+            last_flags = (None if not args.tiled or flag_ptrs is None else
+                          flags if k == 0 else rot_flags[k - 1])
+        arrays = [(f"level_{L}", last[L], dtype) for L in range(1, n_levels)]
+        if last_flags is not None:
+            arrays += [(f"level_{L}_nonzero", last_flags[L], np.uint8)
+                       for L in range(1, n_levels)]
+        dump_outputs(args.dump_outputs, arrays)
     xgmi_node = None
     if node_devices is not None:
         # the node's span per step (rank 0), then the kernel alone: the
@@ -640,7 +704,7 @@ def main():
                                   f"HIP events around the {args.steps} back-to-back launches "
                                   "of the timed region, on the launch stream"),
                 "buffer_sets": n_rot}
-    if n_rot > 1:
+    if args.full and n_rot > 1:
         # the same launches on one buffer set, for contrast: what the cache
         # keeps of a read set this small shows up here, not in `frac`
         kev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -671,21 +735,23 @@ def main():
             for r, c in enumerate(rank_comm_ms):
                 roofline["per_rank"][r]["comm_ms_per_step"] = round(c, 4)
 
-    ceiling = measure_ceiling(torch, stream, d_all, read_bytes, alg_bytes - read_bytes,
-                              max(5, args.steps // 2), n_rot, B * frame_bytes)
+    ceiling = None
+    if args.full:
+        ceiling = measure_ceiling(torch, stream, d_all, read_bytes, alg_bytes - read_bytes,
+                                  max(5, args.steps // 2), n_rot, B * frame_bytes)
     if ceiling is not None:
         ceiling["frac_of_ceiling"] = round(achieved / ceiling["GBps"], 4)
         roofline["same_mix_ceiling"] = ceiling
 
     cpu_baseline = None
     e2e = None
-    if rank == 0 and world == 1 and not args.no_pmc:
+    if args.full and rank == 0 and world == 1 and not args.no_pmc:
         # cascade_kernel or cascade_band_kernel (row bands staged in LDS)
         traffic = measure_traffic(args, "volume_kernel" if Z else "cascade_")
         if traffic is not None:
             roofline["traffic"] = traffic["bytes_per_launch"]
             roofline["traffic_detail"] = traffic
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if args.cpu_seconds > 0:
             nf = min(B, 8)
             frames = d_in[:nf * frame_bytes].cpu().numpy().view(dtype).reshape(nf, H, W)
@@ -731,7 +797,7 @@ def main():
                                                           args.e2e_frames, device,
                                                           os.path.join(args.sink, "w"))
 
-    if world > 1 and args.e2e_frames > 0:
+    if args.full and world > 1 and args.e2e_frames > 0:
         # host-to-host on every GPU at once: each rank over its own PCIe link
         nmulti = min(B, 32)
         e2e_multi = measure_e2e_pipelined(aqz, torch, geo, dtype, method, d_in, nmulti,

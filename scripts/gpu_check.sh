@@ -30,7 +30,7 @@ for s in $STEPS; do
     if fatal $rc; then exit $rc; fi ;;
   bench)
     echo "== bench"
-    timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
+    timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
     rc=$?; echo "bench rc=$rc"; cat "$OUT/bench.json"; tail -5 "$OUT/bench.err"
     [ $rc -eq 0 ] || exit $rc ;;
   prof)
@@ -46,7 +46,7 @@ for s in $STEPS; do
     echo "== rocprofv3 kernel-trace, 8(f) kernels"
     export TMPDIR=/tmp
     timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv \
-      -d "$OUT/prof2" -o run -- python3 "$ROOT/bench.py" --steps 5 --warmup 1 \
+      -d "$OUT/prof2" -o run -- python3 "$ROOT/bench.py" --full --steps 5 --warmup 1 \
       --cpu-seconds 0 --e2e-frames 8 --no-pmc --no-check > "$OUT/prof2.log" 2>&1
     rc=$?; echo "prof2 rc=$rc"; tail -3 "$OUT/prof2.log"
     find "$OUT/prof2" -name "*stats*" | head

@@ -31,8 +31,7 @@ cp "$ref/CMakeLists.txt" "$tree/"
 mkdir -p "$out/lib" "$scratch/inc/nlohmann"
 ln -sf /opt/conda/include/json.hpp "$scratch/inc/nlohmann/json.hpp"
 for f in libblosc.so.1 liblz4.so.1 libz.so.1 libzstd.so.1; do cp -f "/opt/conda/lib/$f" "$out/lib/$f"; done
-ln -sf libblosc.so.1 "$out/lib/libblosc.so"
-ln -sf libzstd.so.1 "$out/lib/libzstd.so"
+# linked by soname (-l:NAME below), so that no libNAME.so links appear under tests/
 
 flags=(-std=c++20 -O2 -fPIC -w -DAQZ_DOWNSAMPLER_HIP -I "$scratch/inc" -I "$repo/include"
        -I "$tree/include" -I "$tree/src/streaming" -I "$tree/src/logger" -idirafter /opt/conda/include)
@@ -48,6 +47,6 @@ for s in "$tree/src/streaming/downsampler.cpp" "$tree/src/streaming/downsampler.
 done
 for p in "${pids[@]}"; do wait "$p"; done
 g++ -o "$out/adapter_harness" "${objs[@]}" \
-  -L "$repo/acquire-zarr_amd" -laqz_downsampler -L "$out/lib" -lblosc -lzstd -lpthread \
+  -L "$repo/acquire-zarr_amd" -laqz_downsampler -L "$out/lib" -l:libblosc.so.1 -l:libzstd.so.1 -lpthread \
   -Wl,-rpath,'$ORIGIN/../../../acquire-zarr_amd' -Wl,-rpath,'$ORIGIN/lib' -Wl,-rpath,/opt/rocm/lib
 echo "built $out/adapter_harness"
