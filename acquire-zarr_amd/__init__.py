@@ -54,6 +54,7 @@ EXPORTS = (
     "aqz_node_add_frame", "aqz_node_take_frame", "aqz_node_flush",
     "aqz_node_run_device_batch", "aqz_node_wait_input", "aqz_ds_wait_input",
     "aqz_node_set_level_tiling", "aqz_ds_input_pending", "aqz_node_inputs_released",
+    "aqz_debug_launch_log",
 )
 
 
@@ -224,6 +225,7 @@ def lib() -> ctypes.CDLL:
     L.aqz_node_inputs_released.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.aqz_node_run_device_batch.argtypes = [vp, vp, i32, u32, ctypes.POINTER(vp),
                                             ctypes.POINTER(u32), vp, u32]
+    L.aqz_debug_launch_log.argtypes = [ctypes.c_char_p, sz]
     _lib = L
     return L
 
@@ -265,6 +267,25 @@ def plan_levels(dims, max_levels: int = 0):
 def level_geometry(levels):
     """(width, height, planes) per level, as add_frame reads them."""
     return [(lv[-1][1], lv[-2][1], lv[-3][1]) for lv in levels]
+
+
+def debug_launch_log():
+    """aqz_debug_launch_log: the launches recorded since the last call (only
+    with $AQZ_LAUNCH_LOG=1 in the environment before the first launch), one
+    dict of the line's key=value fields per launch, oldest first; integer
+    values as int.  Clears the log."""
+    buf = ctypes.create_string_buffer(512 * 321 + 1)
+    rc = lib().aqz_debug_launch_log(buf, len(buf))
+    if rc:
+        raise AqzError(rc, "aqz_debug_launch_log")
+    out = []
+    for line in buf.value.decode().splitlines():
+        rec = {}
+        for kv in line.split():
+            k, _, v = kv.partition("=")
+            rec[k] = int(v) if v.lstrip("-").isdigit() else v
+        out.append(rec)
+    return out
 
 
 def method_name(method: int):

@@ -16,6 +16,7 @@
 // bitshuffle-generic.c; RFC 3720 CRC-32C); the CPU restatement the tests
 // compare against is oracle/codec_oracle.c.
 #include "codec_kernels.hh"
+#include "launch_log.hh"
 
 #include <hip/hip_runtime.h>
 
@@ -351,8 +352,17 @@ filter_run(int shuffle, uint32_t ts, const uint8_t* src, uint8_t* dst, const Blo
     const uint32_t ne = run.bs / ts;
     const bool doshuffle = shuffle == 1 && ts > 1;
     const bool dobit = shuffle == 2 && run.bs >= ts;
+    // launch log (launch_log.hh): the kernel form this run takes
+    auto note = [&](const char* family, const char* form, uint32_t grid, uint32_t block,
+                    uint32_t n) {
+        if (launch_log_on())
+            launch_log_record("family=%s dtype=%u method=%d n_out=1 grid=%u block=%u form=%s "
+                              "waves=%u blocks=%u bs=%u",
+                              family, ts, shuffle, grid, block, form, block / 64, n, run.bs);
+    };
     auto generic = [&](auto kernel) {
         return split_launch(run, n_blocks, run.bs, [&](BlockRun r, uint32_t n, uint32_t grid) {
+            note(doshuffle ? "shuffle" : "bitshuffle", "generic", grid, 256, n);
             hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, src, dst, r, n, ts);
         });
     };
@@ -363,6 +373,7 @@ filter_run(int shuffle, uint32_t ts, const uint8_t* src, uint8_t* dst, const Blo
             return generic(shuffle_generic_kernel);
         return split_launch(run, n_blocks, run.bs / (8 * ts),
                             [&](BlockRun r, uint32_t n, uint32_t grid) {
+            note("shuffle", "vec", grid, 256, n);
             switch (ts) {
                 case 2:
                     hipLaunchKernelGGL(shuffle_vec_kernel<2>, dim3(grid), dim3(256), 0, stream,
@@ -411,6 +422,7 @@ filter_run(int shuffle, uint32_t ts, const uint8_t* src, uint8_t* dst, const Blo
             const uint32_t wv = ts <= 2 ? 1 : 4;
             return split_launch(run, n_blocks, per, [&](BlockRun r, uint32_t n, uint32_t) {
                 const uint32_t grid = uint32_t((uint64_t(per) * n + 64 * wv - 1) / (64 * wv));
+                note("bitshuffle", "bytes", grid, 64 * wv, n);
                 if (ts == 2)
                     hipLaunchKernelGGL((bitshuffle_vec_kernel<2, 1, false>), dim3(grid), dim3(64),
                                        0, stream, src, dst, r, n);
@@ -426,6 +438,7 @@ filter_run(int shuffle, uint32_t ts, const uint8_t* src, uint8_t* dst, const Blo
             const uint32_t per = ne / 8 / G;
             return split_launch(run, n_blocks, per, [&](BlockRun r, uint32_t n, uint32_t) {
                 const uint32_t grid = uint32_t((uint64_t(per) * n + 64 * waves - 1) / (64 * waves));
+                note("bitshuffle", "vec", grid, uint32_t(64 * waves), n);
                 auto go = [&](auto kern) {
                     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * waves), 0, stream, src, dst, r, n);
                 };
@@ -444,6 +457,7 @@ filter_run(int shuffle, uint32_t ts, const uint8_t* src, uint8_t* dst, const Blo
         }
         return split_launch(run, n_blocks, ne / 8 / G,
                             [&](BlockRun r, uint32_t n, uint32_t grid) {
+            note("bitshuffle", "vec", grid, 256, n);
             switch (ts) {
                 case 1:
                     hipLaunchKernelGGL(bitshuffle_vec_kernel<1>, dim3(grid), dim3(256), 0,
@@ -465,6 +479,7 @@ filter_run(int shuffle, uint32_t ts, const uint8_t* src, uint8_t* dst, const Blo
         });
     }
     return split_launch(run, n_blocks, run.bs, [&](BlockRun r, uint32_t n, uint32_t grid) {
+        note("copy", "generic", grid, 256, n);
         hipLaunchKernelGGL(copy_kernel, dim3(grid), dim3(256), 0, stream, src, dst, r, n);
     });
 }

@@ -23,6 +23,25 @@
 // transpose_kernel turns its tiles through LDS.
 #include "ds_kernels.hh"
 
+// The launchers' decision log (launch_log.hh, launch_log.cpp) is part of the
+// library build, which always sets AQZ_SHARDS; a tools/ probe that includes
+// this file directly builds alone and records nothing.
+#ifdef AQZ_SHARDS
+#include "launch_log.hh"
+#else
+namespace aqz {
+inline bool
+launch_log_on()
+{
+    return false;
+}
+inline void
+launch_log_record(const char*, ...)
+{
+}
+} // namespace aqz
+#endif
+
 // Build sharding (acquire-zarr_amd/Makefile): the library compiles this file
 // AQZ_SHARDS times; shard k instantiates the kernels of the dtypes whose
 // code % AQZ_SHARDS == k, and its dtype-dispatching launchers are named
@@ -2601,6 +2620,15 @@ AQZ_SHARDED(launch_cascade)(int dtype,
                                   reinterpret_cast<const void*>(
                                     &cascade_band_kernel<T, M, NLV, C, NT, RW, SP>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+                            if (launch_log_on())
+                                launch_log_record(
+                                  "family=band dtype=%d method=%d n_out=%d grid=%u block=%u "
+                                  "units=%u units_x=%u cols=%d nt=%d upw=1 order=0 remap=0 wb=%u "
+                                  "stage_mask=%u seg_tiles=%u seg_rowwise=%d band_last=%u "
+                                  "seg_w=0 split=%d lds=%u",
+                                  int(sizeof(T)), M, NLV, bands, blk.x, p.total_units,
+                                  p.units_x, C, int(NT), p.wb, stage_mask, seg_tiles, int(RW),
+                                  p.band_last, int(SP), lds);
                             hipLaunchKernelGGL((cascade_band_kernel<T, M, NLV, C, NT, RW, SP>),
                                                dim3(bands), blk, lds, stream, p, stage_mask,
                                                seg_tiles);
@@ -2634,6 +2662,15 @@ AQZ_SHARDED(launch_cascade)(int dtype,
                     launch_band(std::false_type{}, std::false_type{});
                     return;
                 }
+                if (launch_log_on())
+                    launch_log_record(
+                      "family=cascade dtype=%d method=%d n_out=%d grid=%u block=%u units=%u "
+                      "units_x=%u cols=%d nt=%d upw=%u order=%u remap=%u wb=%u stage_mask=0 "
+                      "seg_tiles=0 seg_rowwise=0 band_last=0 seg_w=%u split=0 lds=0",
+                      int(sizeof(T)), M, std::min(n_out, 4), grid_run, 64 * wpb_run,
+                      p.total_units, p.units_x, C, int(NT),
+                      (!p.seg_w && p.order == 0) ? std::max(p.upw, 1u) : 1u, p.order, p.remap,
+                      p.wb, p.seg_w);
                 switch (n_out) {
                     case 1:
                         hipLaunchKernelGGL((cascade_kernel<T, M, 1, C, NT>), dim3(grid_run), dim3(64 * wpb_run),
@@ -2896,6 +2933,14 @@ AQZ_SHARDED(launch_cascade_tiled)(int dtype,
                 constexpr int C = decltype(ctag)::value;
                 constexpr bool NT = decltype(nttag)::value;
                 constexpr int MD = decltype(mdtag)::value;
+                if (launch_log_on())
+                    launch_log_record(
+                      "family=tiled dtype=%d method=%d n_out=%d grid=%u block=%u units=%u "
+                      "units_x=%u cols=%d nt=%d remap=%u seg_w=%u wpb=%u zwaves=%u nested=%d "
+                      "main_blocks=%u",
+                      int(sizeof(T)), M, std::min(n_out, 4), grid, 64 * wpb, p.total_units,
+                      p.units_x, C, int(NT), p.remap, p.seg_w, wpb, p.zwaves, int(MD == 1),
+                      p.main_blocks);
                 switch (n_out) {
                     case 1:
                         hipLaunchKernelGGL((cascade_kernel<T, M, 1, C, NT, MD>), dim3(grid),
@@ -3001,14 +3046,36 @@ AQZ_SHARDED(launch_volume)(int dtype,
         return with_method(method, [&](auto mtag) -> hipError_t {
             constexpr int M = decltype(mtag)::value;
             const bool ntl = nt_env >= 0 ? nt_env != 0 : true;
-            // $AQZ_VOLUME_UPW=4 (A/B, Decimate, nontemporal loads): four
-            // units per wave, 16 KiB of loads in flight per wave
-            const int upw = M == kDecimate ? (upw_env >= 4 ? 4 : upw_env > 0 ? std::min(upw_env, 2) : 2)
+            // $AQZ_VOLUME_UPW=4 (A/B, Decimate): four units per wave, 16 KiB
+            // of loads in flight per wave.  Only the nontemporal-load kernels
+            // are built for four, so with plain loads ($AQZ_VOLUME_NT=0) the
+            // request is clamped to two.  (Until round 6 the grid was sized
+            // for four while the one-unit kernel ran, which left three
+            // quarters of the units unwritten.)  Every launch below sizes its
+            // grid from the UPW its kernel is instantiated with.
+            const int upw = M == kDecimate ? (upw_env >= 4 ? (ntl ? 4 : 2)
+                                              : upw_env > 0 ? std::min(upw_env, 2) : 2)
                                            : 1;
-            const uint32_t grid = grid_for((total + upw - 1) / upw, 4, 0);
-#define AQZ_VOL(NL, NTL, UPW)                                                          \
-    hipLaunchKernelGGL((volume_kernel<T, M, NL, NTL, UPW>), dim3(grid), dim3(256), 0, \
-                       stream, p)
+            auto vol_launch = [&](auto nltag, auto ntltag, auto upwtag, auto zftag) {
+                constexpr int NLK = decltype(nltag)::value;
+                constexpr bool NTL = decltype(ntltag)::value;
+                constexpr int UPW = decltype(upwtag)::value;
+                constexpr bool ZF = decltype(zftag)::value;
+                constexpr int CZ = 16 / int(sizeof(T));
+                const uint32_t grid = grid_for((total + UPW - 1) / UPW, 4, 0);
+                if (launch_log_on())
+                    launch_log_record(
+                      "family=volume dtype=%d method=%d n_out=%d grid=%u block=256 units=%u "
+                      "units_x=%u upw=%d ntl=%d zfast=%d UPW=%d",
+                      int(sizeof(T)), M, NLK, grid, p.total_units, p.units_x, upw, int(NTL),
+                      int(ZF), UPW);
+                hipLaunchKernelGGL((volume_kernel<T, M, NLK, NTL, UPW, CZ, ZF>), dim3(grid),
+                                   dim3(256), 0, stream, p);
+            };
+#define AQZ_VOL_Z(NL, NTL, UPW, ZF)                                                       \
+    vol_launch(std::integral_constant<int, NL>{}, std::integral_constant<bool, NTL>{},    \
+               std::integral_constant<int, UPW>{}, std::integral_constant<bool, ZF>{})
+#define AQZ_VOL(NL, NTL, UPW) AQZ_VOL_Z(NL, NTL, UPW, false)
             // Decimate launches of 128 or more plane groups (two or more
             // config-V volumes) take the plane groups fastest in the unit
             // order, so the units in flight spread over many planes: four
@@ -3021,13 +3088,10 @@ AQZ_SHARDED(launch_volume)(int dtype,
             const bool zfast = zf_env >= 0 ? zf_env != 0 : (n_planes >> n_out) >= 128;
             if constexpr (M == kDecimate) {
                 if (upw == 4 && ntl) {
-                    constexpr int CZ = 16 / int(sizeof(T));
                     if (zfast && n_out == 1)
-                        hipLaunchKernelGGL((volume_kernel<T, M, 1, true, 4, CZ, true>), dim3(grid),
-                                           dim3(256), 0, stream, p);
+                        AQZ_VOL_Z(1, true, 4, true);
                     else if (zfast)
-                        hipLaunchKernelGGL((volume_kernel<T, M, 2, true, 4, CZ, true>), dim3(grid),
-                                           dim3(256), 0, stream, p);
+                        AQZ_VOL_Z(2, true, 4, true);
                     else if (n_out == 1)
                         AQZ_VOL(1, true, 4);
                     else
@@ -3035,13 +3099,10 @@ AQZ_SHARDED(launch_volume)(int dtype,
                     return hipGetLastError();
                 }
                 if (upw == 2 && zfast && ntl) {
-                    constexpr int CZ = 16 / int(sizeof(T));
                     if (n_out == 1)
-                        hipLaunchKernelGGL((volume_kernel<T, M, 1, true, 2, CZ, true>), dim3(grid),
-                                           dim3(256), 0, stream, p);
+                        AQZ_VOL_Z(1, true, 2, true);
                     else
-                        hipLaunchKernelGGL((volume_kernel<T, M, 2, true, 2, CZ, true>), dim3(grid),
-                                           dim3(256), 0, stream, p);
+                        AQZ_VOL_Z(2, true, 2, true);
                     return hipGetLastError();
                 }
                 if (upw == 2) {
@@ -3065,6 +3126,7 @@ AQZ_SHARDED(launch_volume)(int dtype,
             else
                 AQZ_VOL(2, false, 1);
 #undef AQZ_VOL
+#undef AQZ_VOL_Z
             return hipGetLastError();
         });
     });
@@ -3226,6 +3288,9 @@ AQZ_SHARDED(launch_xy_generic)(int dtype,
         using T = decltype(tag);
         return with_method(method, [&](auto mtag) -> hipError_t {
             constexpr int M = decltype(mtag)::value;
+            if (launch_log_on())
+                launch_log_record("family=generic dtype=%d method=%d n_out=1 grid=%u block=256",
+                                  int(sizeof(T)), M, grid);
             hipLaunchKernelGGL((xy_generic_kernel<T, M>),
                                dim3(grid), dim3(256), 0, stream,
                                static_cast<const T*>(src), src_frame_elems, w,
@@ -3261,6 +3326,10 @@ AQZ_SHARDED(launch_zpair)(int dtype,
         using T = decltype(tag);
         return with_method(method, [&](auto mtag) -> hipError_t {
             constexpr int M = decltype(mtag)::value;
+            if (launch_log_on())
+                launch_log_record(
+                  "family=zpair dtype=%d method=%d n_out=1 grid=%u block=256 vec=%d",
+                  int(sizeof(T)), M, grid, int(vec));
             if (vec)
                 hipLaunchKernelGGL((zpair_kernel<T, M, true>), dim3(grid),
                                    dim3(256), 0, stream, static_cast<T*>(out),

@@ -593,6 +593,24 @@ const char* aqz_method_metadata_json(int method);
 /* Library version string. */
 const char* aqz_version(void);
 
+/*
+ * Test seam: the launch log.  With $AQZ_LAUNCH_LOG=1 in the environment when
+ * the library launches its first kernel, every kernel launcher (the fused
+ * cascade and its band form, the chunk-tiled cascade, the fused volume, the
+ * generic XY and Z-pair kernels, the blosc filters) records the kernel it
+ * chose, one line of space-separated key=value pairs per launch, in a
+ * process-wide ring of the last 512 launches; unset, nothing is recorded.
+ * Every line has `family` (cascade, band, tiled, volume, generic, zpair,
+ * shuffle, bitshuffle, copy), `dtype` (bytes per element), `method`, `n_out`,
+ * `grid` and `block`, and the fields of its launcher's A/B switches
+ * (acquire-zarr_amd/csrc/launch_log.hh, tests/test_gpu_launch_rules.py).
+ * Copies the lines, oldest first, each ended by '\n', into `buf` as one
+ * NUL-terminated string and clears the log.  AQZ_OK (an empty string when
+ * nothing was recorded); AQZ_INVALID_ARGUMENT for a null `buf` or `cap` 0;
+ * AQZ_OVERFLOW when `cap` is too small, and the log is kept.  Thread-safe.
+ */
+int aqz_debug_launch_log(char* buf, size_t cap);
+
 /* ---- Frame sharding over a node's GPUs --------------------
  *
  * Frames of a 2-D pyramid are independent, and so are slabs of a volume that

@@ -14,7 +14,7 @@ FILTER_CASES = [
     (2, 65536, 131072, 4),          # 256x256 u16 chunk: two full blocks
     (2, 65536, 65536 * 3 + 4096, 2),  # leftover block, vector path
     (2, 32768, 1000, 3),            # one short block: generic path
-    (1, 4096, 4096 * 5 + 8, 2),     # u8 bitshuffle (G = 16)
+    (1, 4096, 4096 * 5 + 8, 2),     # u8; the second buffer is 8 bytes off 16-B alignment: generic path
     (4, 16384, 16384 * 4, 3),       # u32 / f32
     (8, 16384, 16384 * 2 + 48, 2),  # u64 / f64, leftover of 6 elements
     (16, 8192, 8192 * 2, 2),        # typesize 16

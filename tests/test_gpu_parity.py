@@ -183,26 +183,35 @@ BATCH_GEOMETRIES = {
     # the unit order (round 5); column edges in the second
     "3d_fused_many_groups": ([(64, 32, 8), (32, 16, 4), (16, 8, 2)], 512, 2),
     "3d_fused_many_groups_edge": ([(72, 40, 8), (36, 20, 4), (18, 10, 2)], 520, 2),
-    # level rows that split 64-B bursts: band-staged stores when a row band
-    # is <= 4 tiles (1500 px u16), direct stores from band-aligned
-    # workgroups for wider bands (2600 px u16 / f32, i64)
+    # The schemes named below are pinned for u16 and f32 Mean by
+    # tests/test_gpu_launch_rules.py (DEFAULT_PINS), from the launch log.
+    # Level rows that split 64-B bursts: the whole band staged in LDS and
+    # stored by its last wave when it is <= 6 tiles of 16 bytes per lane or
+    # <= 4 of 32 (1500 px: 3 tiles; 2600 px u16: 6), direct stores from one
+    # workgroup per band for wider bands (2600 px f32: 6 wide tiles)
     "2d_wide_misaligned": (halving_geometry(2600, 70, 4), 3, 1),
     "2d_band_staged": (halving_geometry(1500, 90, 4), 3, 1),
-    # aligned row bands of 5-8 tiles: every level staged by 8-wave (u16, f32
-    # with 85 KiB of LDS) or 6-wave workgroups; u8 / i64 keep direct stores
+    # aligned row bands: every level staged behind a barrier.  3072 px u16:
+    # the whole 6-tile band in a 6-wave workgroup; 4096 px u16: 8 tiles, in
+    # 3-tile segments for Mean and Decimate, 4-tile ones for Min / Max.  f32
+    # and i64 rows of whole KiB take 16-byte tiles (12 to 32 per band here),
+    # so they go in 8-tile segments like the next entry; u8 4096 px is one
+    # 4-tile band
     "2d_band8_aligned": (halving_geometry(4096, 48, 4), 3, 1),
     "2d_band6_edge_rows": (halving_geometry(3072, 37, 4), 3, 1),
-    # aligned bands wider than 8 tiles: 8-tile segments (u8 9 tiles, u16 /
-    # f32 17, i64 34), a last segment of one or two tiles, odd band rows
+    # aligned bands wider than 8 tiles: 8-tile segments (u8 9 tiles, u16 17,
+    # f32 34, i64 68), a last segment of one to four tiles, odd band rows
     "2d_band_segments": (halving_geometry(8704, 40, 4), 2, 1),
-    # misaligned bands of up to 8 tiles in band-aligned workgroups (round
-    # 3): 8 tiles (u16 / f32) with an odd band at the bottom; a last tile of
-    # 10 px, so deep levels hold bursts shared by three waves
+    # misaligned bands too wide to stage whole, up to 8 tiles: direct stores
+    # from one workgroup per band (round 3).  3900 px: 8 tiles (u16 / f32)
+    # with an odd band at the bottom.  2570 px: a last tile of 10 px, so deep
+    # levels hold bursts shared by three waves; f32 takes the 6-wave
+    # workgroup, u16 (6 tiles) is staged whole and stored by its last wave
     "2d_complete_8tile": (halving_geometry(3900, 37, 4), 2, 1),
     "2d_complete_short_last": (halving_geometry(2570, 50, 4), 3, 1),
     # misaligned bands of more than 8 tiles (u16 / f32: 10): balanced 4-tile
     # segments, every level row its own LDS piece, stored by the segment's
-    # last wave; odd band at the bottom
+    # last two waves (level 1's rows split bursts); odd band at the bottom
     "2d_mis_segments": (halving_geometry(4700, 41, 4), 2, 1),
 }
 
