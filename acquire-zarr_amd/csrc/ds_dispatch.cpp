@@ -1,192 +1,148 @@
-// ds_dispatch.cpp — routes each dtype-dispatching launcher of ds_kernels.hh
-// to the build shard that instantiates that dtype's kernels.
+// ds_dispatch.cpp — the host entry of every launcher of ds_kernels.hh.
+//
+// launch_cascade, launch_cascade_tiled and launch_volume plan here
+// (ds_plan.hh: the process-wide switches, the device's LDS cap), record the
+// plan's line in the launch log and hand the plan to run_cascade,
+// run_cascade_tiled or run_volume of the dtype's kernel shard; the other
+// launchers are routed as they are.
 //
 // ds_kernels.hip is compiled AQZ_SHARDS times (acquire-zarr_amd/Makefile);
 // shard k holds the kernels of the dtypes whose code % AQZ_SHARDS == k and
-// names its launchers <launcher>_shard<k>.  This file is compiled once.
+// names its launchers <launcher>_shard<k>.  This file is compiled once.  A
+// tools/ probe includes it after ds_kernels.hip, unsharded: the three planned
+// launchers then call the one set of run_* functions.
 #include "ds_kernels.hh"
 
 #ifndef AQZ_SHARDS
 #error "ds_dispatch.cpp is built with -DAQZ_SHARDS=<n> (acquire-zarr_amd/Makefile)"
 #endif
-#if AQZ_SHARDS != 8
+#if AQZ_SHARDS != 8 && AQZ_SHARDS != 1
 #error "ds_dispatch.cpp routes to exactly 8 shards"
+#endif
+#if AQZ_SHARDS > 1
+#include "launch_log.hh"
 #endif
 
 namespace aqz {
 
+#if AQZ_SHARDS > 1
+#define AQZ_SHARD_FNS(name)                                                    \
+    name##_shard0, name##_shard1, name##_shard2, name##_shard3, name##_shard4, \
+      name##_shard5, name##_shard6, name##_shard7
+
 #define AQZ_DECLARE_SHARDS(name, params)                                       \
-    hipError_t name##_shard0 params;                                           \
-    hipError_t name##_shard1 params;                                           \
-    hipError_t name##_shard2 params;                                           \
-    hipError_t name##_shard3 params;                                           \
-    hipError_t name##_shard4 params;                                           \
-    hipError_t name##_shard5 params;                                           \
-    hipError_t name##_shard6 params;                                           \
-    hipError_t name##_shard7 params;
+    using name##_fn = hipError_t params;                                       \
+    name##_fn AQZ_SHARD_FNS(name);
 
 #define AQZ_ROUTE(name, dtype, args)                                           \
     do {                                                                       \
+        static constexpr decltype(&name##_shard0) shard[] = { AQZ_SHARD_FNS(name) }; \
         if (!dtype_valid(dtype))                                               \
             return hipErrorInvalidValue;                                       \
-        switch ((dtype) % AQZ_SHARDS) {                                        \
-            case 0:                                                            \
-                return name##_shard0 args;                                     \
-            case 1:                                                            \
-                return name##_shard1 args;                                     \
-            case 2:                                                            \
-                return name##_shard2 args;                                     \
-            case 3:                                                            \
-                return name##_shard3 args;                                     \
-            case 4:                                                            \
-                return name##_shard4 args;                                     \
-            case 5:                                                            \
-                return name##_shard5 args;                                     \
-            case 6:                                                            \
-                return name##_shard6 args;                                     \
-            default:                                                           \
-                return name##_shard7 args;                                     \
-        }                                                                      \
+        return shard[(dtype) % AQZ_SHARDS] args;                               \
     } while (0)
 
-AQZ_DECLARE_SHARDS(launch_cascade,
-                   (int, int, const void*, uint64_t, uint32_t, uint32_t, const LevelOut*, int,
-                    uint32_t, hipStream_t))
-AQZ_DECLARE_SHARDS(launch_cascade_tiled,
-                   (int, int, const void*, uint64_t, uint32_t, uint32_t, const LevelOut*,
-                    const TiledOut*, int, uint32_t, hipStream_t))
-AQZ_DECLARE_SHARDS(launch_volume,
-                   (int, int, const void*, uint64_t, uint32_t, uint32_t, const LevelOut*, int,
-                    uint32_t, hipStream_t))
-AQZ_DECLARE_SHARDS(launch_xy_generic,
-                   (int, int, const void*, uint64_t, uint32_t, uint32_t, const LevelOut&,
-                    uint32_t, hipStream_t))
-AQZ_DECLARE_SHARDS(launch_zpair,
-                   (int, int, void*, const void*, const void*, uint64_t, hipStream_t))
-AQZ_DECLARE_SHARDS(launch_transpose,
-                   (int, const void*, uint32_t, uint32_t, void*, hipStream_t))
-AQZ_DECLARE_SHARDS(launch_tile_frame,
-                   (int, const void*, uint32_t, uint32_t, uint32_t, uint32_t, void*, uint32_t*,
-                    hipStream_t))
-AQZ_DECLARE_SHARDS(launch_tile_frame_sliced,
-                   (int, const void*, uint32_t, uint32_t, uint32_t, uint32_t, void*, uint8_t*,
-                    hipStream_t))
+AQZ_DECLARE_SHARDS(run_cascade,
+                   (const CascadePlan&, const void*, uint64_t, uint32_t, uint32_t,
+                    const LevelOut*, hipStream_t))
+AQZ_DECLARE_SHARDS(run_cascade_tiled,
+                   (const TiledPlan&, const void*, uint64_t, uint32_t, uint32_t, const LevelOut*,
+                    const TiledOut*, hipStream_t))
+AQZ_DECLARE_SHARDS(run_volume,
+                   (const VolumePlan&, const void*, uint64_t, uint32_t, uint32_t,
+                    const LevelOut*, hipStream_t))
+#else
+#define AQZ_ROUTE(name, dtype, args) return name args
+#endif
+
+namespace {
+
+// LDS a band workgroup may use: the device's per-workgroup maximum (160 KiB
+// on gfx950), 64 KiB if the query fails, less the band kernel's static
+// arrival counter.  Asked once per process.
+uint32_t
+device_lds_cap()
+{
+    static const uint32_t cap = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) == hipSuccess &&
+            hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) ==
+              hipSuccess &&
+            v > 16)
+            return uint32_t(v) - 16u;
+        return 65536u;
+    }();
+    return cap;
+}
+
+} // namespace
 
 hipError_t
-launch_cascade(int dtype,
-               int method,
-               const void* src,
-               uint64_t src_frame_elems,
-               uint32_t W,
-               uint32_t H,
-               const LevelOut* outs,
-               int n_out,
-               uint32_t n_frames,
-               hipStream_t stream)
+launch_cascade(int dtype, int method, const void* src, uint64_t src_frame_elems, uint32_t W,
+               uint32_t H, const LevelOut* outs, int n_out, uint32_t n_frames, hipStream_t stream)
 {
-    AQZ_ROUTE(launch_cascade, dtype,
-              (dtype, method, src, src_frame_elems, W, H, outs, n_out, n_frames, stream));
+    const CascadePlan pl = plan_cascade(dtype, method, src, src_frame_elems, W, H, outs, n_out,
+                                        n_frames, device_lds_cap(), launch_switches());
+    if (!pl.valid)
+        return hipErrorInvalidValue;
+    if (launch_log_on())
+        launch_log_record("%s", format_plan(pl).c_str());
+    AQZ_ROUTE(run_cascade, dtype, (pl, src, src_frame_elems, W, H, outs, stream));
 }
 
 hipError_t
-launch_cascade_tiled(int dtype,
-                     int method,
-                     const void* src,
-                     uint64_t src_frame_elems,
-                     uint32_t W,
-                     uint32_t H,
-                     const LevelOut* outs,
-                     const TiledOut* touts,
-                     int n_out,
-                     uint32_t n_frames,
-                     hipStream_t stream)
+launch_cascade_tiled(int dtype, int method, const void* src, uint64_t src_frame_elems,
+                     uint32_t W, uint32_t H, const LevelOut* outs, const TiledOut* touts,
+                     int n_out, uint32_t n_frames, hipStream_t stream)
 {
-    AQZ_ROUTE(launch_cascade_tiled, dtype,
-              (dtype, method, src, src_frame_elems, W, H, outs, touts, n_out, n_frames, stream));
+    const TiledPlan pl = plan_cascade_tiled(dtype, method, src, src_frame_elems, W, H, outs,
+                                            touts, n_out, n_frames, launch_switches());
+    if (!pl.valid)
+        return hipErrorInvalidValue;
+    if (launch_log_on())
+        launch_log_record("%s", format_plan(pl).c_str());
+    AQZ_ROUTE(run_cascade_tiled, dtype, (pl, src, src_frame_elems, W, H, outs, touts, stream));
 }
 
 hipError_t
-launch_volume(int dtype,
-              int method,
-              const void* src,
-              uint64_t src_frame_elems,
-              uint32_t W,
-              uint32_t H,
-              const LevelOut* outs,
-              int n_out,
-              uint32_t n_planes,
-              hipStream_t stream)
+launch_volume(int dtype, int method, const void* src, uint64_t src_frame_elems, uint32_t W,
+              uint32_t H, const LevelOut* outs, int n_out, uint32_t n_planes, hipStream_t stream)
 {
-    AQZ_ROUTE(launch_volume, dtype,
-              (dtype, method, src, src_frame_elems, W, H, outs, n_out, n_planes, stream));
+    const VolumePlan pl = plan_volume(dtype, method, src, src_frame_elems, W, H, outs, n_out,
+                                      n_planes, launch_switches());
+    if (!pl.valid)
+        return hipErrorInvalidValue;
+    if (launch_log_on())
+        launch_log_record("%s", format_plan(pl).c_str());
+    AQZ_ROUTE(run_volume, dtype, (pl, src, src_frame_elems, W, H, outs, stream));
 }
 
-hipError_t
-launch_xy_generic(int dtype,
-                  int method,
-                  const void* src,
-                  uint64_t src_frame_elems,
-                  uint32_t w,
-                  uint32_t h,
-                  const LevelOut& out,
-                  uint32_t n_frames,
-                  hipStream_t stream)
-{
-    AQZ_ROUTE(launch_xy_generic, dtype,
-              (dtype, method, src, src_frame_elems, w, h, out, n_frames, stream));
-}
+#if AQZ_SHARDS > 1
+// The launchers that only route: each shard's has the launcher's own type.
+#define AQZ_FORWARD(name, params, args)                                        \
+    decltype(name) AQZ_SHARD_FNS(name);                                        \
+    hipError_t name params { AQZ_ROUTE(name, dtype, args); }
 
-hipError_t
-launch_zpair(int dtype,
-             int method,
-             void* out,
-             const void* earlier,
-             const void* current,
-             uint64_t n,
-             hipStream_t stream)
-{
-    AQZ_ROUTE(launch_zpair, dtype, (dtype, method, out, earlier, current, n, stream));
-}
-
-hipError_t
-launch_transpose(int dtype,
-                 const void* src,
-                 uint32_t rows,
-                 uint32_t cols,
-                 void* dst,
-                 hipStream_t stream)
-{
-    AQZ_ROUTE(launch_transpose, dtype, (dtype, src, rows, cols, dst, stream));
-}
-
-hipError_t
-launch_tile_frame(int dtype,
-                  const void* src,
-                  uint32_t W,
-                  uint32_t H,
-                  uint32_t tile_rows,
-                  uint32_t tile_cols,
-                  void* dst,
-                  uint32_t* nonzero,
-                  hipStream_t stream)
-{
-    AQZ_ROUTE(launch_tile_frame, dtype,
-              (dtype, src, W, H, tile_rows, tile_cols, dst, nonzero, stream));
-}
-
-hipError_t
-launch_tile_frame_sliced(int dtype,
-                         const void* src,
-                         uint32_t W,
-                         uint32_t H,
-                         uint32_t tile_rows,
-                         uint32_t tile_cols,
-                         void* dst,
-                         uint8_t* slice_flags,
-                         hipStream_t stream)
-{
-    AQZ_ROUTE(launch_tile_frame_sliced, dtype,
-              (dtype, src, W, H, tile_rows, tile_cols, dst, slice_flags, stream));
-}
+AQZ_FORWARD(launch_xy_generic,
+            (int dtype, int method, const void* src, uint64_t src_frame_elems, uint32_t w,
+             uint32_t h, const LevelOut& out, uint32_t n_frames, hipStream_t stream),
+            (dtype, method, src, src_frame_elems, w, h, out, n_frames, stream))
+AQZ_FORWARD(launch_zpair,
+            (int dtype, int method, void* out, const void* earlier, const void* current,
+             uint64_t n, hipStream_t stream),
+            (dtype, method, out, earlier, current, n, stream))
+AQZ_FORWARD(launch_transpose,
+            (int dtype, const void* src, uint32_t rows, uint32_t cols, void* dst,
+             hipStream_t stream),
+            (dtype, src, rows, cols, dst, stream))
+AQZ_FORWARD(launch_tile_frame,
+            (int dtype, const void* src, uint32_t W, uint32_t H, uint32_t tile_rows,
+             uint32_t tile_cols, void* dst, uint32_t* nonzero, hipStream_t stream),
+            (dtype, src, W, H, tile_rows, tile_cols, dst, nonzero, stream))
+AQZ_FORWARD(launch_tile_frame_sliced,
+            (int dtype, const void* src, uint32_t W, uint32_t H, uint32_t tile_rows,
+             uint32_t tile_cols, void* dst, uint8_t* slice_flags, hipStream_t stream),
+            (dtype, src, W, H, tile_rows, tile_cols, dst, slice_flags, stream))
+#endif // AQZ_SHARDS > 1
 
 } // namespace aqz

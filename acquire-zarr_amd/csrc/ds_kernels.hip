@@ -23,6 +23,8 @@
 // transpose_kernel turns its tiles through LDS.
 #include "ds_kernels.hh"
 
+// What the fused launchers launch is decided on the host (ds_plan.cpp);
+// ds_dispatch.cpp hands the plan to run_cascade, run_cascade_tiled, run_volume.
 // The launchers' decision log (launch_log.hh, launch_log.cpp) is part of the
 // library build, which always sets AQZ_SHARDS; a tools/ probe that includes
 // this file directly builds alone and records nothing.
@@ -45,10 +47,11 @@ launch_log_record(const char*, ...)
 // Build sharding (acquire-zarr_amd/Makefile): the library compiles this file
 // AQZ_SHARDS times; shard k instantiates the kernels of the dtypes whose
 // code % AQZ_SHARDS == k, and its dtype-dispatching launchers are named
-// <launcher>_shard<k>.  ds_dispatch.cpp routes each call to its shard, and
-// shard 0 alone defines the dtype-independent helpers.  The shards compile
-// in parallel: one unit held over a thousand kernel instantiations.  Included
-// directly (the tools/ probes), the file builds unsharded.
+// <launcher>_shard<k>.  ds_dispatch.cpp routes each call to its shard; the
+// dtype-independent helpers are ds_plan.cpp's.  The shards compile in
+// parallel: one unit held over a thousand kernel instantiations.  Included
+// directly (the tools/ probes, followed by ds_plan.cpp and ds_dispatch.cpp),
+// the file builds unsharded.
 #ifndef AQZ_SHARDS
 #define AQZ_SHARDS 1
 #endif
@@ -64,8 +67,6 @@ launch_log_record(const char*, ...)
 #endif
 
 #include <algorithm>
-#include <cstdlib>
-#include <cstring>
 #include <type_traits>
 
 namespace aqz {
@@ -83,14 +84,6 @@ typedef u32x4 u32x4_u __attribute__((aligned(1)));
 typedef uint64_t u64_u __attribute__((aligned(1)));
 typedef uint32_t u32_u __attribute__((aligned(1)));
 typedef uint16_t u16_u __attribute__((aligned(1)));
-
-enum
-{
-    kDecimate = 0,
-    kMean = 1,
-    kMin = 2,
-    kMax = 3
-};
 
 // ---- reducers --------------------------------------------------------------
 
@@ -608,90 +601,6 @@ struct CascadeParams
     uint32_t upw;                    // units per wave (cascade_kernel, columns-fastest order)
 };
 
-// $AQZ_LOAD_NT: 1 / 0 forces the fused cascade's loads with / without the
-// non-temporal hint (A/B only); unset (-1): the launcher decides.
-inline int
-load_nt_env()
-{
-    static const int v = [] {
-        const char* e = std::getenv("AQZ_LOAD_NT");
-        return (e && *e) ? std::atoi(e) : -1;
-    }();
-    return v;
-}
-
-// Non-temporal loads unless the frame rows are not whole 128-B lines: there a
-// line straddles two waves' row segments, and without the streaming hint the
-// second wave finds it in L2 (3000^2 u16: 2.7% fewer read requests, 4%
-// faster; aligned rows lose 6% without the hint; profiles/r02/loadnt_ab.log).
-inline uint32_t
-load_nt(uint32_t W, size_t bpp)
-{
-    if (load_nt_env() >= 0)
-        return load_nt_env() != 0;
-    return (uint64_t(W) * bpp) % 128 == 0;
-}
-
-// $AQZ_TILED_ZWAVES: unset = the launcher's count of zero-fill waves, else
-// that count (A/B only; 0 skips the zero fill and leaves the overhang
-// unwritten).
-inline int
-tiled_zwaves_env()
-{
-    static const int v = [] {
-        const char* e = std::getenv("AQZ_TILED_ZWAVES");
-        return (e && *e) ? std::atoi(e) : -1;
-    }();
-    return v;
-}
-
-// $AQZ_STORE_WB: unset = the launcher's default, else a level bit mask
-// (bit J-1 = level J) of row-major stores issued write-back instead of
-// non-temporal (A/B).
-inline int
-store_wb_env()
-{
-    static const int v = [] {
-        const char* e = std::getenv("AQZ_STORE_WB");
-        return (e && *e) ? std::atoi(e) : -1;
-    }();
-    return v;
-}
-
-// $AQZ_UNIT_ORDER (0 columns fastest = default, 1 frames fastest, 2 row bands
-// fastest) and $AQZ_CASCADE_WAVES (waves per workgroup, 4 = default, up to
-// 8): A/B switches of the row-major cascade's unit-to-wave mapping.
-inline int
-int_env(const char* name, int dflt)
-{
-    const char* e = std::getenv(name);
-    return (e && *e) ? std::atoi(e) : dflt;
-}
-
-// $AQZ_SPLIT_LOADS: 1 / 0 = band kernels of 4- and 8-byte types load each
-// row's 2 KiB wave segment as two contiguous halves (cascade_unit SPLIT) or
-// as 32 bytes per lane; unset: the launcher's default.
-inline bool
-split_loads()
-{
-    static const bool v = [] {
-        const char* e = std::getenv("AQZ_SPLIT_LOADS");
-        return (e && *e) ? std::atoi(e) != 0 : false;
-    }();
-    return v;
-}
-
-// $AQZ_XCD_REMAP: unset = the launcher's default, 0 = off, 1 = on (A/B only).
-inline int
-xcd_remap_env()
-{
-    static const int v = [] {
-        const char* e = std::getenv("AQZ_XCD_REMAP");
-        return (e && *e) ? std::atoi(e) : -1;
-    }();
-    return v;
-}
-
 // Columns of T per lane in the fused cascade: 16 bytes for 1- and 2-byte
 // types, 32 bytes (two 16-byte loads per row) for 4- and 8-byte types, which
 // keeps levels 1-3 in-lane and halves the cross-lane shuffles.  A/B on
@@ -699,12 +608,6 @@ xcd_remap_env()
 // bit-identical; the same widening measured slower for u16 (562 vs 470 us).
 template<typename T>
 constexpr int kCascadeCols = sizeof(T) >= 4 ? 32 / int(sizeof(T)) : 16 / int(sizeof(T));
-
-inline uint32_t
-cascade_cols(size_t bpp)
-{
-    return uint32_t((bpp >= 4 ? 32 : 16) / bpp);
-}
 
 // Lanes per column group at level J when each lane starts with C columns.
 template<int C, int J>
@@ -1570,47 +1473,6 @@ cascade_band_kernel(CascadeParams p, uint32_t stage_mask, uint32_t seg_tiles)
     }
 }
 
-// LDS a band workgroup may use: the device's per-workgroup maximum (160 KiB
-// on gfx950, so f32 bands of 8 waves, 85 KiB, fit), 64 KiB if the query
-// fails; $AQZ_BAND_LDS_CAP (bytes) lowers it for A/B.
-inline uint32_t
-band_lds_cap()
-{
-    static const uint32_t cap = [] {
-        int dev = 0, v = 0;
-        uint32_t c = 65536;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) ==
-              hipSuccess &&
-            v > 16)
-            c = uint32_t(v) - 16u; // the kernel's static arrival counter
-        const int e = int_env("AQZ_BAND_LDS_CAP", 0);
-        return e > 0 ? std::min(c, uint32_t(e)) : c;
-    }();
-    return cap;
-}
-
-// Bytes of LDS cascade_band_kernel needs for a band (upper bound over
-// bands; 0 if no level is staged).
-inline uint32_t
-band_lds_bytes(size_t b, const LevelOut* outs, int n_out, uint32_t stage_mask,
-               uint32_t seg_cols = 0, bool rowwise = false)
-{
-    uint64_t total = 0;
-    for (int i = 0; i < n_out; ++i) {
-        if ((stage_mask >> i) & 1u) {
-            const uint64_t rows = uint64_t(1) << (n_out - i - 1);
-            const uint64_t w = seg_cols ? std::min<uint64_t>(seg_cols >> (i + 1), outs[i].w)
-                                        : outs[i].w;
-            if (rowwise)
-                total += rows * ((w * b + 30) & ~uint64_t(15)); // StageCtx::rowb slots
-            else
-                total += (15 + rows * w * b + 15) & ~uint64_t(15);
-        }
-    }
-    return total > (1u << 30) ? (1u << 30) : uint32_t(total);
-}
-
 // ---- fused volume (2x2x2, two-stage) ----------------------------------------
 //
 // For pyramids whose every level halves XY *and* Z (3-D stacks, BASELINE
@@ -2193,954 +2055,268 @@ with_method(int method, F&& f)
     }
 }
 
-
-uint32_t
-grid_for(uint64_t work_items, uint32_t per_block, uint32_t cap)
+// The fused launches write 1..kMaxFusedLevels levels.
+template<typename F>
+hipError_t
+with_levels(int n_out, F&& f)
 {
-    uint64_t blocks = (work_items + per_block - 1) / per_block;
-    if (blocks < 1)
-        blocks = 1;
-    if (cap && blocks > cap)
-        blocks = cap;
-    return uint32_t(blocks);
-}
-
-} // namespace
-#if AQZ_SHARD == 0
-
-size_t
-dtype_bytes(int dtype)
-{
-    switch (dtype) {
-        case 0:
-        case 4:
-            return 1;
+    switch (n_out) {
         case 1:
-        case 5:
-            return 2;
+            return f(std::integral_constant<int, 1>{});
         case 2:
-        case 6:
-        case 8:
-            return 4;
+            return f(std::integral_constant<int, 2>{});
         case 3:
-        case 7:
-        case 9:
-            return 8;
+            return f(std::integral_constant<int, 3>{});
+        case 4:
+            return f(std::integral_constant<int, 4>{});
         default:
-            return 0;
-    }
-}
-#endif
-#if AQZ_SHARD == 0
-
-bool
-dtype_valid(int dtype)
-{
-    return dtype_bytes(dtype) != 0;
-}
-#endif
-#if AQZ_SHARD == 0
-
-bool
-method_valid(int method)
-{
-    return method >= kDecimate && method <= kMax;
-}
-#endif
-
-
-#if AQZ_SHARD == 0
-namespace {
-
-// Can the fused cascade run this level run with C columns per lane?
-bool
-cascade_fits(size_t b,
-             const void* src,
-             uint64_t src_frame_elems,
-             uint32_t W,
-             uint32_t H,
-             const LevelOut* outs,
-             int n_out,
-             uint32_t C)
-{
-    if (!b || C == 0 || n_out < 1 || n_out > kMaxFusedLevels || W == 0 || H == 0)
-        return false;
-    // Frames of any width and byte offset: loads and stores take any
-    // alignment; a lane straddling a row end loads one vector (load_chunk)
-    // and stores element by element (store_level).  Needs element-aligned
-    // buffers and a row of at least one load (E elements); narrower frames
-    // take the single-level kernels.
-    const size_t lb = std::min<size_t>(16, size_t(C) * b);
-    if (reinterpret_cast<uintptr_t>(src) % b != 0 || W < lb / b)
-        return false;
-    uint32_t w = W, h = H;
-    for (int i = 0; i < n_out; ++i) {
-        w = (w + 1) / 2;
-        h = (h + 1) / 2;
-        if (outs[i].w != w || outs[i].h != h)
-            return false;
-        if (reinterpret_cast<uintptr_t>(outs[i].ptr) % b != 0)
-            return false;
-    }
-    return true;
-}
-
-} // namespace
-#endif
-#if AQZ_SHARD == 0
-
-// 16-byte tiles for 4- and 8-byte types: rows whose level 1-4 rows are all
-// whole 64-B bursts (cascade_pick_cols, cascade_tiled_cols)
-static bool
-narrow_rows(size_t b, uint32_t W)
-{
-    return b >= 4 && (uint64_t(W) * b) % 1024 == 0;
-}
-
-uint32_t
-cascade_pick_cols(int dtype,
-                  const void* src,
-                  uint64_t src_frame_elems,
-                  uint32_t W,
-                  uint32_t H,
-                  const LevelOut* outs,
-                  int n_out)
-{
-    const size_t b = dtype_bytes(dtype);
-    if (!b)
-        return 0;
-    // wide tiles (kCascadeCols) where a wave's 64 lanes fit in the frame;
-    // half-width tiles for narrower frames (a 512-px u8 frame would leave half
-    // of every wide wave idle on the edge path) and for widths only the
-    // narrow tile divides
-    const uint32_t cw = cascade_cols(b), cn = cw / 2;
-    const bool wide = cascade_fits(b, src, src_frame_elems, W, H, outs, n_out, cw);
-    const bool narrow = cascade_fits(b, src, src_frame_elems, W, H, outs, n_out, cn);
-    // 4-byte types on rows of whole 128-B lines take 16-byte tiles too (4
-    // columns per lane: 73 VGPRs, 6 waves per SIMD, against 138 VGPRs and 3
-    // waves for 32-byte tiles) now that such rows leave through LDS-staged
-    // bands: 4096^2 f32 Mean 985 -> 948 us, Max 992 -> 946, Decimate 604 ->
-    // 583, 8192x2048 947 -> 903, 3072^2 1105 -> 1018 (profiles/r05/narrow/;
-    // round 1, before band staging, had measured the opposite, 1083 -> 975
-    // us for the wide tiles).  Rows that split lines keep the wide tiles and
-    // their misaligned segments: 5472x3648 1091 against 1206 us narrow,
-    // 6000x4000 1049 against 1150, 2000^2 1085 against 1123.  The same holds
-    // for the other 4- and 8-byte types at 4096^2: u32 Mean 994 -> 947 us,
-    // f64 Mean 1034 -> 884, f64 Max 1056 -> 889 (profiles/r05/widths/).
-    // "Whole lines" must hold for the levels too, not only level 0: f32
-    // 5472x3648 (21888-B rows, level 2 splits bursts) ran 1155 us narrow
-    // against 1065-1091 wide (profiles/r05/shapes/), so the rule asks for
-    // W * b a multiple of 1024 (levels 1-4 rows whole 64-B bursts).
-    // $AQZ_CASCADE_NARROW=0/1 (A/B) forces wide / narrow for 4- and 8-byte
-    // types.
-    static const int narrow_env = int_env("AQZ_CASCADE_NARROW", -1);
-    const bool prefer_narrow = narrow_env >= 0 ? (narrow_env != 0 && b >= 4)
-                                               : narrow_rows(b, W);
-    if (prefer_narrow && narrow)
-        return cn;
-    if (wide && W >= 64 * cw)
-        return cw;
-    if (narrow)
-        return cn;
-    return wide ? cw : 0;
-}
-#endif
-#if AQZ_SHARD == 0
-
-bool
-cascade_supported(int dtype,
-                  const void* src,
-                  uint64_t src_frame_elems,
-                  uint32_t W,
-                  uint32_t H,
-                  const LevelOut* outs,
-                  int n_out)
-{
-    return cascade_pick_cols(dtype, src, src_frame_elems, W, H, outs, n_out) != 0;
-}
-#endif
-
-hipError_t
-AQZ_SHARDED(launch_cascade)(int dtype,
-               int method,
-               const void* src,
-               uint64_t src_frame_elems,
-               uint32_t W,
-               uint32_t H,
-               const LevelOut* outs,
-               int n_out,
-               uint32_t n_frames,
-               hipStream_t stream)
-{
-    const uint32_t cols = cascade_pick_cols(dtype, src, src_frame_elems, W, H, outs, n_out);
-    if (cols == 0 || n_frames == 0)
-        return hipErrorInvalidValue;
-
-    return with_dtype(dtype, [&](auto tag) -> hipError_t {
-        using T = decltype(tag);
-        constexpr uint32_t CW = kCascadeCols<T>;
-        constexpr uint32_t CN = CW / 2;
-        CascadeParams p{};
-        p.src = static_cast<const uint8_t*>(src);
-        p.src_frame_elems = src_frame_elems;
-        p.W = W;
-        p.H = H;
-        p.units_x = (W + 64 * cols - 1) / (64 * cols);
-        const uint32_t R = 1u << n_out;
-        p.units_y = (H + R - 1) / R;
-        const uint64_t total = uint64_t(p.units_x) * p.units_y * n_frames;
-        if (total >= (1ull << 31))
             return hipErrorInvalidValue;
-        p.total_units = uint32_t(total);
-        for (int i = 0; i < n_out; ++i) {
-            p.dst[i] = static_cast<uint8_t*>(outs[i].ptr);
-            p.dst_frame_elems[i] = outs[i].frame_elems;
-            p.w[i] = outs[i].w;
-            p.h[i] = outs[i].h;
-        }
-        // 4 waves per block, one tile per wave per iteration.
-        static const uint32_t wpb = uint32_t(std::clamp(int_env("AQZ_CASCADE_WAVES", 4), 1, 8));
-        static const uint32_t order = uint32_t(std::clamp(int_env("AQZ_UNIT_ORDER", 0), 0, 2));
-        // Units per wave (cascade_kernel's loop): a Decimate wave whose unit
-        // reads under 4 KiB takes 2, 4 or 8 consecutive units, so that it
-        // moves at least that much: 512^2 u8 Decimate (1 KiB read per unit)
-        // 55.3 -> 40.7 us with 4 (8: 45.8).  Other methods keep one unit per
-        // wave and, where that unit is under 4 KiB, load plain: 512^2 u8
-        // Mean 61.4-62.0 -> 59.4-59.8 us, Max 61.8 -> 60.6-61.2 against two
-        // units with nontemporal loads.  Round 5, with the input and output
-        // in HBM (rotating buffer sets); round 4's
-        // two-unit Mean/Max choice had been timed with the whole read set
-        // resident in the Infinity Cache.  2048^2 u16 Decimate (4 KiB units)
-        // keeps 1 (two: 76.5 -> 78.8-80.1 us).  $AQZ_UNITS_PER_WAVE=k forces k.
-        static const int upw_env = int_env("AQZ_UNITS_PER_WAVE", 0);
-        uint32_t upw = 1;
-        bool small_plain = false;
-        if (upw_env > 0) {
-            upw = uint32_t(std::min(upw_env, 16));
-        } else {
-            const uint64_t unit_bytes = (uint64_t(R) * 64u * cols * sizeof(T)) >>
-                                        (method == kDecimate ? 1 : 0);
-            if (method == kDecimate) {
-                while (upw < 8 && unit_bytes * upw < 4096)
-                    upw *= 2;
-            } else {
-                small_plain = unit_bytes < 4096;
-            }
-        }
-        p.upw = order == 0 ? upw : 1u;
-        const uint32_t grid = grid_for((total + p.upw - 1) / p.upw, wpb, 0);
-        p.main_blocks = grid;
-        p.order = order;
-        p.remap = xcd_remap_env() == 1;
-        p.wb = store_wb_env() >= 0 ? uint32_t(store_wb_env()) : 0u;
-        p.nt = load_nt(W, sizeof(T));
-        // Loads keep the nontemporal hint on aligned rows, Decimate's looped
-        // small units included (512^2 u8 Decimate 40.7 us against 42.1-42.5
-        // plain, with the data in HBM; the round-5 plain-load rule had been
-        // timed with its 128 MiB read set resident in the Infinity Cache,
-        // DESIGN.md §11.11), except the small single units above.
-        if (load_nt_env() < 0 && small_plain)
-            p.nt = 0;
-        // Band staging when some level's rows are not whole 64-byte bursts
-        // and a row band is at most 4 tiles, 6 for 2-byte types
-        // ($AQZ_BAND_STAGING=0: never; $AQZ_BAND_MIS_MAX: the widest such
-        // band).  These bands are stored by their last wave to finish
-        // (p.band_last = 1), not after a barrier: any wait for the band's
-        // slowest wave cost more than staging saves (u16 3000^2 805 us with
-        // a barrier, 594 / 676 us with the last two / three waves storing,
-        // 546 us with the last one, against 575 us for direct stores;
-        // profiles/r03/misaligned/last_wave_ab.log).  Against the barrier
-        // form of <= 4 tiles and direct stores above (mis6_edges_ab.log):
-        // u16 2000^2 570 -> 523 us, 2304^2 565 -> 498, 3000^2 575 -> 549,
-        // 2600^2 538 -> 547; u8 3000^2 104 -> 85; f32 2000^2 unchanged.
-        // One wave storing a wider band is too slow: u16 4000x3000 (8 tiles)
-        // 557 -> 627 us, u8 5000x4000 (5 tiles) 91 -> 101, f32 3000^2 (6
-        // tiles, 64 KiB) 1095 -> 1442, so those keep direct stores.  Aligned
-        // bands keep the barrier, where all waves share the stores (4096^2
-        // f32 987 us against 1026 / 1058 us).  $AQZ_BAND_LAST=K forces the
-        // last K waves to store every band (0: the barrier).  Also tried and
-        // dropped: waves storing the bursts inside their own tile from
-        // registers and the last wave only the shared ones (5-27% slower).
-        static const int band_last_env = int_env("AQZ_BAND_LAST", -1);
-        static const int mis_max_env = int_env("AQZ_BAND_MIS_MAX", -1);
-        // 16-byte tiles of 4-byte types move 1 KiB per row per wave, as the
-        // 2-byte tiles do, so they share the 2-byte thresholds
-        const bool tile16 = sizeof(T) == 2 || (sizeof(T) == 4 && cols == CN);
-        const uint32_t mis_max = mis_max_env >= 0 ? uint32_t(std::min(mis_max_env, 8))
-                                                  : (tile16 ? 6u : 4u);
-        static const int mis_seg_env = std::min(int_env("AQZ_BAND_MIS_SEG", -1), 8);
-        uint32_t stage_mask = 0;
-        for (int i = 0; i < n_out; ++i) {
-            const bool whole = (uint64_t(outs[i].w) * sizeof(T)) % 64 == 0 &&
-                               (outs[i].frame_elems * sizeof(T)) % 64 == 0 &&
-                               reinterpret_cast<uintptr_t>(outs[i].ptr) % 64 == 0;
-            if (!whole)
-                stage_mask |= 1u << i;
-        }
-        static const bool band_off = [] {
-            const char* v = std::getenv("AQZ_BAND_STAGING");
-            return v && std::strcmp(v, "0") == 0;
-        }();
-        // Aligned frames of 4-8 tiles per row band (the headline's 4096 u16
-        // pixels, 3072, 4096 f32, config C2's 2048 u16) stage every level
-        // too, in workgroups of one wave per tile, so each level's band
-        // leaves as one contiguous span.  4-tile bands joined in round 5,
-        // timed with the data in HBM (rotating buffer sets): C2 Mean 123.0-
-        // 123.5 -> 118.1-118.4 us, Decimate 76.7-76.9 -> 72.1-72.4
-        // (profiles/r05/c2knobs/ab.log).
-        // On most MI355X boxes tried, row-major level rows at a >= 4 KiB
-        // pitch written 512 B per wave ran 15-20% below the same kernel with
-        // tile-order stores; staged bands remove that (headline 535 -> 463
-        // us, 3072^2 541 -> 448 us; profiles/r02/band8_*).
-        // $AQZ_BAND_ALIGNED=0 turns this off; $AQZ_BAND_FORCE (A/B) stages a
-        // level mask whatever the alignment, in bands of up to 8 waves.
-        // Aligned bands wider than 8 tiles go in 8-tile segments, one
-        // workgroup each, every level row of a segment one contiguous piece:
-        // 8192x2048 u16 517 -> 485 us, 8704x2040 532 -> 447 us, 6144x3072
-        // 531 -> 516 us, 8192x2048 f32 1012 -> 962 us
-        // (profiles/r02/band8/segments_ab.log); $AQZ_BAND_SEGMENTS=0: off.
-        static const uint32_t band_force = uint32_t(int_env("AQZ_BAND_FORCE", 0));
-        static const bool band_aligned = int_env("AQZ_BAND_ALIGNED", 1) != 0;
-        static const bool band_segments = int_env("AQZ_BAND_SEGMENTS", 1) != 0;
-        uint32_t band_waves = p.units_x;
-        const uint32_t all_levels = (1u << n_out) - 1u;
-        uint32_t wide_max = mis_max, seg_tiles = 0;
-        const bool misaligned = stage_mask != 0;
-        p.band_last = band_last_env >= 0 ? uint32_t(std::min(band_last_env, 8))
-                                         : (misaligned ? 1u : 0u);
-        if (band_force) {
-            stage_mask |= band_force & all_levels;
-            wide_max = 8;
-        } else if (band_aligned && stage_mask == 0 && band_waves >= 4 && band_waves <= 8 &&
-                   band_lds_bytes(sizeof(T), outs, n_out, all_levels) <= band_lds_cap()) {
-            stage_mask = all_levels;
-            wide_max = 8;
-            // 8-tile bands go in segments (first measured as two of 4 tiles,
-            // below): a whole 4096 f32 band
-            // needs 85 KiB of LDS, one workgroup per CU, whose loads and
-            // stores then never overlap; segments fit two or three.  Same
-            // box, two rounds (profiles/r03/f32/band_seg4_ab.log): f32 Max
-            // 1062 -> 999 us, Mean 1042 -> 991, Min 1064 -> 998, the headline
-            // 478 -> 473; 6-tile bands lost (3072^2 470 -> 510), so only
-            // bands of 8.  $AQZ_BAND_SEG4=0 / 1: never / always.
-            // Tiles per segment: 3 (segments of 3, 3, 2) for 2-byte Mean and
-            // for Decimate, 4 otherwise.  Same box, two rounds each
-            // (profiles/r03/f32/segment_tiles_ab*.log): headline (u16 Mean)
-            // 473-475 -> 462-463 us, 4096x2160 469-473 -> 461-462, u16
-            // Decimate 297 -> 294, f32 Decimate 644-652 -> 607-608; but u16
-            // Min/Max 472-474 -> 480-483 and f32 Mean/Min/Max 990-1000 ->
-            // 1027-1030, which keep 4.  $AQZ_BAND_SEGN overrides (A/B).
-            static const int seg4 = int_env("AQZ_BAND_SEG4", -1);
-            static const int segn_env = int_env("AQZ_BAND_SEGN", 0);
-            const uint32_t segn = segn_env > 0 ? uint32_t(std::min(segn_env, 8))
-                                  : (method == kDecimate || (method == kMean && sizeof(T) == 2))
-                                    ? 3u : 4u;
-            if (seg4 == 1 || (seg4 < 0 && band_waves == 8)) {
-                seg_tiles = segn;
-                band_waves = segn;
-            }
-        } else if (band_aligned && band_segments && stage_mask == 0 && band_waves > 8 &&
-                   band_lds_bytes(sizeof(T), outs, n_out, all_levels, 8u * 64u * cols) <=
-                     band_lds_cap()) {
-            stage_mask = all_levels;
-            seg_tiles = 8;
-            band_waves = 8;
-            wide_max = 8;
-        } else if (misaligned && band_waves > mis_max && (sizeof(T) == 2 || sizeof(T) == 4) &&
-                   // exactly the tiles the dispatch below builds a rowwise
-                   // (RW) band kernel for (2-byte narrow tiles
-                   // have none)
-                   (cols == CW || (sizeof(T) == 4 && cols == CN)) &&
-                   (mis_seg_env > 0 || (mis_seg_env < 0 && band_waves > 8))) {
-            // Misaligned bands of more than 8 tiles (2- and 4-byte types, wide
-            // tiles): balanced segments of at most 4 tiles
-            // ($AQZ_BAND_MIS_SEG: any band of those types wider than one
-            // wave may store, segments of that many tiles; 0: never), each staged and stored by its last wave,
-            // every level row of a segment its own piece (StageCtx::rowb);
-            // only the pieces' ends share bursts with the neighbouring
-            // segments.  Same box, two rounds, against band workgroups with
-            // direct stores (profiles/r03/misaligned/mis_segments_ab*.log):
-            // f32 5472x3648 1264 -> 1092 us, 6000x4000 1167 -> 1104, 4100^2
-            // 1150 -> 1077; u16 6000x4000 585 -> 557, 5472x3648 534 -> 530.
-            // Narrower bands lost or tied (u16 4000x3000 557 -> 612 us, f32
-            // 3000^2 1099 -> 1428), and u8 gained only at exactly 6 tiles in
-            // 2-tile segments, so those keep direct stores.
-            const uint32_t mis_seg = mis_seg_env > 0 ? uint32_t(mis_seg_env) : 4u;
-            const uint32_t nseg = (p.units_x + mis_seg - 1) / mis_seg;
-            seg_tiles = (p.units_x + nseg - 1) / nseg;
-            band_waves = seg_tiles;
-            p.seg_rowwise = 1;
-            // these segments are stored by their last two waves when level
-            // 1's rows split bursts: u16 6000x4000 556 -> 543 us, 5472x3648
-            // 535 -> 523, 4100^2 597 -> 582, f32 6000x4000 1085 -> 1045,
-            // 4100^2 1074 -> 1060; but f32 5472x3648 (level 1 whole bursts)
-            // 1087 -> 1117, so it keeps one (same box, two rounds,
-            // profiles/r04/misseg/).  Whole misaligned bands of <= 6 tiles
-            // keep one too (3000^2 548-550 -> 600 us with two).
-            if (band_last_env < 0)
-                p.band_last = (stage_mask & 1u) ? 2u : 1u;
-        }
-        const uint32_t lds = band_lds_bytes(sizeof(T), outs, n_out, stage_mask,
-                                            seg_tiles * 64u * cols, p.seg_rowwise != 0);
-        const bool band = stage_mask && !band_off &&
-                          band_waves <= wide_max && lds <= band_lds_cap() &&
-                          total < (1ull << 31);
-        const uint32_t segs = seg_tiles ? (p.units_x + seg_tiles - 1) / seg_tiles : 1u;
-        const uint32_t bands = p.units_y * n_frames * segs;
-        // Direct stores of rows that split 64-B bursts, bands wider than the
-        // staged form takes: one workgroup per band (or per balanced piece
-        // of <= 8 tiles), so a burst shared by neighbouring waves is written
-        // through one L2.  3000^2 622 -> 576 us, 2600^2 601 -> 540 us,
-        // 5472x3648 571 -> 540 us against 4-wave blocks that straddle bands
-        // (profiles/r03/misaligned/); $AQZ_BAND_WG=0: off.
-        static const bool band_wg = int_env("AQZ_BAND_WG", 1) != 0;
-        uint32_t wpb_run = wpb;
-        uint32_t grid_run = grid;
-        if (!band && band_wg && stage_mask && !band_force && p.order == 0 && p.units_x > 4) {
-            const uint32_t nseg = (p.units_x + 7) / 8;
-            p.seg_w = (p.units_x + nseg - 1) / nseg;
-            wpb_run = p.seg_w;
-            grid_run = nseg * p.units_y * n_frames;
-            p.main_blocks = grid_run;
-        }
-        return with_method(method, [&](auto mtag) -> hipError_t {
-            constexpr int M = decltype(mtag)::value;
-            auto go = [&](auto ctag, auto nttag) {
-                constexpr int C = decltype(ctag)::value;
-                constexpr bool NT = decltype(nttag)::value;
-                if (band) {
-                    const dim3 blk(64 * band_waves);
-                    auto launch_band = [&](auto rtag, auto stag) {
-                        constexpr bool RW = decltype(rtag)::value;
-                        constexpr bool SP = decltype(stag)::value;
-                        auto one = [&](auto ltag) {
-                            constexpr int NLV = decltype(ltag)::value;
-                            if (lds > 65536) // above the default per-workgroup LDS
-                                (void)hipFuncSetAttribute(
-                                  reinterpret_cast<const void*>(
-                                    &cascade_band_kernel<T, M, NLV, C, NT, RW, SP>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-                            if (launch_log_on())
-                                launch_log_record(
-                                  "family=band dtype=%d method=%d n_out=%d grid=%u block=%u "
-                                  "units=%u units_x=%u cols=%d nt=%d upw=1 order=0 remap=0 wb=%u "
-                                  "stage_mask=%u seg_tiles=%u seg_rowwise=%d band_last=%u "
-                                  "seg_w=0 split=%d lds=%u",
-                                  int(sizeof(T)), M, NLV, bands, blk.x, p.total_units,
-                                  p.units_x, C, int(NT), p.wb, stage_mask, seg_tiles, int(RW),
-                                  p.band_last, int(SP), lds);
-                            hipLaunchKernelGGL((cascade_band_kernel<T, M, NLV, C, NT, RW, SP>),
-                                               dim3(bands), blk, lds, stream, p, stage_mask,
-                                               seg_tiles);
-                        };
-                        switch (n_out) {
-                            case 1: one(std::integral_constant<int, 1>{}); break;
-                            case 2: one(std::integral_constant<int, 2>{}); break;
-                            case 3: one(std::integral_constant<int, 3>{}); break;
-                            default: one(std::integral_constant<int, 4>{}); break;
-                        }
-                    };
-                    // misaligned segments: a separate instantiation, so that
-                    // whole bands keep their code (a runtime branch per row
-                    // cost 3000^2 / 2600^2 u16 8-9%), for 2- and 4-byte types
-                    // at the wide tile only (where the launcher picks them)
-                    if constexpr ((sizeof(T) == 2 || sizeof(T) == 4) &&
-                                  (C == int(CW) || (sizeof(T) == 4 && C == int(CN)))) {
-                        if (p.seg_rowwise) {
-                            launch_band(std::true_type{}, std::false_type{});
-                            return;
-                        }
-                    }
-                    // whole-line loads for 4- and 8-byte types at the wide
-                    // tile (cascade_unit SPLIT); $AQZ_SPLIT_LOADS=0 / 1 (A/B)
-                    if constexpr (sizeof(T) >= 4 && C == int(CW)) {
-                        if (split_loads()) {
-                            launch_band(std::false_type{}, std::true_type{});
-                            return;
-                        }
-                    }
-                    launch_band(std::false_type{}, std::false_type{});
-                    return;
-                }
-                if (launch_log_on())
-                    launch_log_record(
-                      "family=cascade dtype=%d method=%d n_out=%d grid=%u block=%u units=%u "
-                      "units_x=%u cols=%d nt=%d upw=%u order=%u remap=%u wb=%u stage_mask=0 "
-                      "seg_tiles=0 seg_rowwise=0 band_last=0 seg_w=%u split=0 lds=0",
-                      int(sizeof(T)), M, std::min(n_out, 4), grid_run, 64 * wpb_run,
-                      p.total_units, p.units_x, C, int(NT),
-                      (!p.seg_w && p.order == 0) ? std::max(p.upw, 1u) : 1u, p.order, p.remap,
-                      p.wb, p.seg_w);
-                switch (n_out) {
-                    case 1:
-                        hipLaunchKernelGGL((cascade_kernel<T, M, 1, C, NT>), dim3(grid_run), dim3(64 * wpb_run),
-                                           0, stream, p);
-                        break;
-                    case 2:
-                        hipLaunchKernelGGL((cascade_kernel<T, M, 2, C, NT>), dim3(grid_run), dim3(64 * wpb_run),
-                                           0, stream, p);
-                        break;
-                    case 3:
-                        hipLaunchKernelGGL((cascade_kernel<T, M, 3, C, NT>), dim3(grid_run), dim3(64 * wpb_run),
-                                           0, stream, p);
-                        break;
-                    default:
-                        hipLaunchKernelGGL((cascade_kernel<T, M, 4, C, NT>), dim3(grid_run), dim3(64 * wpb_run),
-                                           0, stream, p);
-                        break;
-                }
-            };
-            auto go_c = [&](auto nttag) {
-                if (cols == CW)
-                    go(std::integral_constant<int, int(CW)>{}, nttag);
-                else
-                    go(std::integral_constant<int, int(CN)>{}, nttag);
-            };
-            if (p.nt)
-                go_c(std::true_type{});
-            else
-                go_c(std::false_type{});
-            return hipGetLastError();
-        });
-    });
+    }
 }
 
-#if AQZ_SHARD == 0
-
-uint32_t
-cascade_tiled_cols(int dtype, uint32_t W)
-{
-    // cascade_pick_cols for element-aligned buffers: wide tiles once a wave's
-    // 64 lanes fit in the frame, half-width ones below
-    const size_t b = dtype_bytes(dtype);
-    if (!b)
-        return 0;
-    const uint32_t cw = cascade_cols(b);
-    // $AQZ_TILED_NARROW (A/B): 1 half-width tiles wherever they fit, 0 wide;
-    // unset: half-width for 4- and 8-byte types on rows whose levels are
-    // whole bursts (narrow_rows), as cascade_pick_cols (the streaming path writes a run tiled in one launch
-    // only when both agree): chunk-tiled 4096^2 f32 964-979 against
-    // 995-1033 us wide; 5472x3648, 6000x4000 and 2000^2 keep wide tiles
-    // (1113 / 990 / 1031 against 1129 / 1074 / 1055 us narrow;
-    // profiles/r05/narrow/ab_shapes.log)
-    static const int narrow = int_env("AQZ_TILED_NARROW", -1);
-    if ((narrow == 1 || (narrow < 0 && narrow_rows(b, W))) &&
-        W >= 64 * (cw / 2))
-        return cw / 2;
-    return W >= 64 * cw ? cw : cw / 2;
-}
-
-uint32_t
-cascade_tiled_slots(int dtype,
-                    uint32_t W,
-                    int n_out,
-                    int level,
-                    uint32_t tile_rows,
-                    uint32_t tile_cols,
-                    uint32_t* slots_x)
-{
-    const uint32_t cols = cascade_tiled_cols(dtype, W);
-    const uint32_t cw = (64u * cols) >> level;       // level columns per wave block
-    const uint32_t rh = (1u << n_out) >> level;      // level rows per wave block
-    const uint32_t co = std::max(1u, cols >> level); // columns per lane store
-    if (slots_x)
-        *slots_x = 1;
-    if (cols == 0 || level < 1 || level > n_out || tile_rows == 0 || tile_cols == 0 ||
-        tile_rows % rh != 0)
-        return 0;
-    // blocks inside tiles: one slot per block; blocks spanning whole tiles
-    // (and lane stores inside one tile): one slot per (tile, block row)
-    uint32_t sx = 0;
-    if (tile_cols % cw == 0)
-        sx = tile_cols / cw;
-    else if (cw % tile_cols == 0 && tile_cols % co == 0)
-        sx = 1;
-    if (sx == 0)
-        return 0;
-    if (slots_x)
-        *slots_x = sx;
-    return (tile_rows / rh) * sx;
-}
-#endif
-
+template<typename F>
 hipError_t
-AQZ_SHARDED(launch_cascade_tiled)(int dtype,
-                                  int method,
-                                  const void* src,
-                                  uint64_t src_frame_elems,
-                                  uint32_t W,
-                                  uint32_t H,
-                                  const LevelOut* outs,
-                                  const TiledOut* touts,
-                                  int n_out,
-                                  uint32_t n_frames,
-                                  hipStream_t stream)
+with_flag(bool on, F&& f)
 {
-    // the flag layout (cascade_tiled_slots) assumes the geometry-only choice;
-    // cascade_pick_cols != 0 says the buffers and level sizes fit the fused
-    // cascade (its conditions do not depend on the tile width)
-    const uint32_t cols = cascade_tiled_cols(dtype, W);
-    const size_t b = dtype_bytes(dtype);
-    if (cols == 0 || n_frames == 0 ||
-        cascade_pick_cols(dtype, src, src_frame_elems, W, H, outs, n_out) == 0)
-        return hipErrorInvalidValue;
-    const uint32_t R = 1u << n_out;
-    CascadeParams p{};
+    return on ? f(std::true_type{}) : f(std::false_type{});
+}
+
+template<int K>
+using int_tag = std::integral_constant<int, K>;
+
+// The source, units and row-major levels of CascadeParams / VolumeParams.
+template<typename P, typename Plan>
+void
+fill_frames(P& p, const Plan& pl, const void* src, uint64_t src_frame_elems, uint32_t W,
+            uint32_t H, const LevelOut* outs)
+{
     p.src = static_cast<const uint8_t*>(src);
     p.src_frame_elems = src_frame_elems;
     p.W = W;
     p.H = H;
-    // The grid's blocks cover the frame; zero-fill waves cover the rest of
-    // the padded tile area.
-    p.units_x = (W + 64 * cols - 1) / (64 * cols);
-    p.units_y = (H + R - 1) / R;
-    const uint64_t total = uint64_t(p.units_x) * p.units_y * n_frames;
-    if (total >= (1ull << 30))
-        return hipErrorInvalidValue;
-    p.total_units = uint32_t(total);
-    bool flag_fill = false;
-    bool nested = true; // every level's wave blocks and tiles nest: mode 1
-    for (int i = 0; i < n_out; ++i) {
-        const TiledOut& t = touts[i];
-        if (!t.ptr || t.tile_rows == 0 || t.tile_cols == 0 ||
-            reinterpret_cast<uintptr_t>(t.ptr) % b != 0)
-            return hipErrorInvalidValue;
-        const uint32_t ntx = (outs[i].w + t.tile_cols - 1) / t.tile_cols;
-        const uint32_t nty = (outs[i].h + t.tile_rows - 1) / t.tile_rows;
-        const uint64_t pw = uint64_t(ntx) * t.tile_cols, ph = uint64_t(nty) * t.tile_rows;
-        if (pw >= (1ull << 31) || ph >= (1ull << 31))
-            return hipErrorInvalidValue;
+    p.units_x = pl.units_x;
+    p.units_y = pl.units_y;
+    p.total_units = pl.total_units;
+    for (int i = 0; i < pl.n_out; ++i) {
         p.dst[i] = static_cast<uint8_t*>(outs[i].ptr);
         p.dst_frame_elems[i] = outs[i].frame_elems;
         p.w[i] = outs[i].w;
         p.h[i] = outs[i].h;
+    }
+}
+
+} // namespace
+
+// The three planned launchers: the plan (ds_plan.hh) has decided everything;
+// these fill the kernel parameters from it and pick the instantiation its
+// selector fields name.  A selector value no kernel is built for is an error,
+// never another kernel.
+
+hipError_t
+AQZ_SHARDED(run_cascade)(const CascadePlan& pl, const void* src, uint64_t src_frame_elems,
+                         uint32_t W, uint32_t H, const LevelOut* outs, hipStream_t stream)
+{
+    if (!pl.valid)
+        return hipErrorInvalidValue;
+    CascadeParams p{};
+    fill_frames(p, pl, src, src_frame_elems, W, H, outs);
+    p.main_blocks = pl.main_blocks;
+    p.remap = pl.remap;
+    p.wb = pl.wb;
+    p.order = pl.order;
+    p.seg_w = pl.seg_w;
+    p.nt = pl.nt;
+    p.band_last = pl.band_last;
+    p.seg_rowwise = pl.seg_rowwise;
+    p.upw = pl.upw;
+    const dim3 grid(pl.grid), block(pl.block);
+    return with_dtype(pl.dtype, [&](auto tag) -> hipError_t {
+        using T = decltype(tag);
+        constexpr int CW = kCascadeCols<T>;
+        constexpr int CN = CW / 2;
+        auto go = [&](auto mtag, auto ltag, auto nttag, auto ctag) -> hipError_t {
+            constexpr int M = decltype(mtag)::value;
+            constexpr int NL = decltype(ltag)::value;
+            constexpr bool NT = decltype(nttag)::value;
+            constexpr int C = decltype(ctag)::value;
+            if (!pl.band) {
+                hipLaunchKernelGGL((cascade_kernel<T, M, NL, C, NT>), grid, block, 0, stream, p);
+                return hipGetLastError();
+            }
+            auto band = [&](auto rtag, auto stag) -> hipError_t {
+                constexpr bool RW = decltype(rtag)::value;
+                constexpr bool SP = decltype(stag)::value;
+                if (pl.lds > 65536) // above the default per-workgroup LDS
+                    (void)hipFuncSetAttribute(
+                      reinterpret_cast<const void*>(&cascade_band_kernel<T, M, NL, C, NT, RW, SP>),
+                      hipFuncAttributeMaxDynamicSharedMemorySize, int(pl.lds));
+                hipLaunchKernelGGL((cascade_band_kernel<T, M, NL, C, NT, RW, SP>), grid, block,
+                                   pl.lds, stream, p, pl.stage_mask, pl.seg_tiles);
+                return hipGetLastError();
+            };
+            // misaligned segments: a separate instantiation, so that
+            // whole bands keep their code (a runtime branch per row
+            // cost 3000^2 / 2600^2 u16 8-9%), for 2- and 4-byte types
+            // at the wide tile only (where the planner picks them)
+            if (pl.seg_rowwise) {
+                if constexpr ((sizeof(T) == 2 || sizeof(T) == 4) &&
+                              (C == CW || (sizeof(T) == 4 && C == CN)))
+                    return band(std::true_type{}, std::false_type{});
+                else
+                    return hipErrorInvalidValue;
+            }
+            // whole-line loads for 4- and 8-byte types at the wide tile
+            // (cascade_unit SPLIT)
+            if (pl.split) {
+                if constexpr (sizeof(T) >= 4 && C == CW)
+                    return band(std::false_type{}, std::true_type{});
+                else
+                    return hipErrorInvalidValue;
+            }
+            return band(std::false_type{}, std::false_type{});
+        };
+        return with_method(pl.method, [&](auto mtag) -> hipError_t {
+            return with_levels(pl.n_out, [&](auto ltag) -> hipError_t {
+                return with_flag(pl.nt != 0, [&](auto nttag) -> hipError_t {
+                    if (pl.cols == uint32_t(CW))
+                        return go(mtag, ltag, nttag, int_tag<CW>{});
+                    if (pl.cols == uint32_t(CN))
+                        return go(mtag, ltag, nttag, int_tag<CN>{});
+                    return hipErrorInvalidValue;
+                });
+            });
+        });
+    });
+}
+
+hipError_t
+AQZ_SHARDED(run_cascade_tiled)(const TiledPlan& pl, const void* src, uint64_t src_frame_elems,
+                               uint32_t W, uint32_t H, const LevelOut* outs,
+                               const TiledOut* touts, hipStream_t stream)
+{
+    if (!pl.valid)
+        return hipErrorInvalidValue;
+    CascadeParams p{};
+    fill_frames(p, pl, src, src_frame_elems, W, H, outs);
+    for (int i = 0; i < pl.n_out; ++i) {
+        const TiledOut& t = touts[i];
+        const TiledLevelPlan& l = pl.lv[i];
         TiledLevel& q = p.tl[i];
         q.tdst = static_cast<uint8_t*>(t.ptr);
-        q.tframe_elems = pw * ph;
+        q.flags = t.nonzero;
+        q.tframe_elems = l.tframe_elems;
         q.foff = t.frame_offsets;
-        q.tstride = t.frame_offsets ? t.tile_stride : uint64_t(t.tile_rows) * t.tile_cols;
-        if (q.tstride < uint64_t(t.tile_rows) * t.tile_cols)
-            return hipErrorInvalidValue;
+        q.tstride = l.tstride;
         q.tr = t.tile_rows;
         q.tc = t.tile_cols;
+        q.ntx = l.ntx;
+        q.pw = l.pw;
+        q.ph = l.ph;
+        q.slots = l.slots;
+        q.slots_x = l.slots_x;
+        q.flags_frame = l.flags_frame;
+        q.cov_w = l.cov_w;
+        q.cov_h = l.cov_h;
+        q.zrows = l.zrows;
         q.dr = FastDiv::make(t.tile_rows);
         q.dc = FastDiv::make(t.tile_cols);
-        q.ntx = ntx;
-        q.pw = uint32_t(pw);
-        q.ph = uint32_t(ph);
-        q.cov_w = p.units_x * ((64u * cols) >> (i + 1));
-        q.cov_h = p.units_y * (R >> (i + 1));
-        q.zrows = q.cov_w < pw ? uint32_t(ph) : (q.cov_h < ph ? uint32_t(ph) - q.cov_h : 0u);
-        p.zitems += q.zrows;
-        q.slots = cascade_tiled_slots(dtype, W, n_out, i + 1, t.tile_rows, t.tile_cols,
-                                      &q.slots_x);
-        if (!q.slots)
-            nested = false;
-        q.flags = t.nonzero;
-        q.flags_frame = ntx * nty * std::max<uint32_t>(1, q.slots);
-        if (t.nonzero && q.slots && (q.cov_w < pw || q.cov_h < ph))
-            flag_fill = true;
-        if (t.nonzero && !q.slots) {
-            // one flag per tile, OR-ed by plain stores of 1: cleared first
+        if (l.clear_flags) {
             const hipError_t e =
-              hipMemsetAsync(t.nonzero, 0, size_t(n_frames) * ntx * nty, stream);
+              hipMemsetAsync(t.nonzero, 0, size_t(pl.n_frames) * l.ntx * l.nty, stream);
             if (e != hipSuccess)
                 return e;
         }
     }
-    // zero-fill waves: a whole number of 8-block (one per XCD) groups
-    const uint64_t zitems = uint64_t(p.zitems) * n_frames;
-    if (zitems >= (1ull << 32))
-        return hipErrorInvalidValue;
-    p.zdiv = FastDiv::make(p.zitems ? p.zitems : 1);
-    // One zero-fill wave per 128 KiB of overhang (64..4096).  The waves run
-    // first and hold their slots while the cascade blocks start; one per
-    // item (up to 4096) cost 4-5% at 3000^2 and 5472x3648 against 512, and
-    // putting them after the cascade blocks made them the kernel's tail
-    // (profiles/r02/tiled_zero_fill_ab.log).
-    uint64_t zbytes = 0;
-    for (int i = 0; i < n_out; ++i) {
-        const TiledLevel& q = p.tl[i];
-        const uint64_t cw = std::min(q.cov_w, q.pw), chh = std::min(q.cov_h, q.ph);
-        zbytes += (uint64_t(q.pw) * q.ph - cw * chh) * b;
-    }
-    zbytes *= n_frames;
-    // ... and for 1-byte types at most ZI = 32 overhang rows per wave: each
-    // row is a short dependent loop, and the byte rule left u8 pyramids
-    // (chunk 128, rows of a few dozen bytes) with thousands of rows per
-    // wave, the kernel's tail.  Same box (profiles/r04/zrows/ab.log): u8
-    // 2600^2 262 -> 111 us, 2304^2 273 -> 131, 1500^2 189 -> 113, 3000^2
-    // 141 -> 93, 5000x4000 100 -> 81; the same cap cost u16 2-4% (3000^2
-    // 516-519 -> 528-531 us), so wider types keep the byte rule.
-    // $AQZ_TILED_ZROWS_PER_WAVE: ZI for every type (0: the byte rule alone).
-    static const int zi_env = int_env("AQZ_TILED_ZROWS_PER_WAVE", -1);
-    const int zi = zi_env >= 0 ? zi_env : (b == 1 ? 32 : 0);
-    uint64_t zw = (zbytes >> 17) + 1;
-    if (zi > 0)
-        zw = std::max<uint64_t>(zw, (zitems + zi - 1) / uint64_t(zi));
-    p.zwaves = (zitems || flag_fill)
-                 ? uint32_t(std::min<uint64_t>(std::max<uint64_t>(zw, 64), 4096))
-                 : 0u;
-    if (const int zw = tiled_zwaves_env(); zw >= 0)
-        p.zwaves = uint32_t(zw); // A/B only: 0 leaves the overhang unwritten
-    p.remap = xcd_remap_env() == 1;
-    // Nontemporal loads on aligned rows for every unit size: with the data
-    // in HBM (rotating buffer sets) chunk-tiled 2048^2
-    // u16 Decimate runs 73.8-73.9 us with them against 79.0-79.7 plain, and
-    // 512^2 u8 Decimate / Mean 73.1-73.5 / 82.6-82.7 against 74.1 / 83.4-
-    // 84.8.  (A round-5 plain-load rule for units of <= 4 KiB had been timed
-    // with the read set resident in the Infinity Cache.)
-    p.nt = load_nt(W, b);
-    // $AQZ_TILED_BAND_WG=1 (A/B, off by default): on rows that split 128-B
-    // lines, one workgroup per row band (or balanced piece of <= 8 tiles), as
-    // the row-major launcher does, so that the two waves sharing a line read
-    // it through one L2.  Reads drop to 1.00-1.01x the frame (from 1.02-1.05x)
-    // but every shape got slower: u16 3000^2 543 -> 615 us, 5472x3648 517 ->
-    // 610, 6000x4000 503 -> 597, 2000^2 507 -> 511, f32 6000x4000 990 -> 1111
-    // (same box, two rounds, profiles/r04/tiledwg/).
-    static const bool band_wg = int_env("AQZ_TILED_BAND_WG", 0) != 0;
-    uint32_t wpb = 4;
-    if (band_wg && !p.remap && (uint64_t(W) * b) % 128 != 0 && p.units_x > 1) {
-        const uint32_t nseg = (p.units_x + 7) / 8;
-        p.seg_w = (p.units_x + nseg - 1) / nseg;
-        wpb = p.seg_w;
-        p.main_blocks = nseg * p.units_y * n_frames;
-    } else {
-        // Waves per workgroup: 4 when a row band's tile count divides by 4,
-        // else 2.  Same box, two rounds (profiles/r04/tiledwaves/): u16
-        // 3000^2 541-549 -> 518-521 us, 2304^2 614-621 -> 576-577, 3500^2
-        // 552 -> 519, 4600x3000 531 -> 510, f32 5472x3648 1191-1193 -> 1116-
-        // 1118, u8 6000x4000 89-96 -> 80-85; but 2-wave blocks lose where 4
-        // divide the band (u16 2000^2 505 -> 580, 6000x4000 505 -> 546-550,
-        // f32 6000x4000 989 -> 1063), and 3-wave blocks lose on 6 tiles
-        // (3000^2 574-576).  $AQZ_TILED_WAVES (1..8) forces a count (A/B).
-        static const int tw = int_env("AQZ_TILED_WAVES", 0);
-        wpb = tw > 0 ? uint32_t(std::min(tw, 8)) : (p.units_x % 4 == 0 ? 4u : 2u);
-        p.main_blocks = grid_for(total, wpb, 0);
-    }
-    // zero-fill blocks: a whole number of 8-block (one per XCD) groups
-    const uint32_t zblocks = ((p.zwaves + wpb - 1) / wpb + 7) & ~7u;
-    p.zwaves = zblocks * wpb;
-    const uint32_t grid = zblocks + p.main_blocks;
-
-    return with_dtype(dtype, [&](auto tag) -> hipError_t {
+    p.zitems = pl.zitems;
+    p.zdiv = FastDiv::make(pl.zitems ? pl.zitems : 1);
+    p.zwaves = pl.zwaves;
+    p.main_blocks = pl.main_blocks;
+    p.remap = pl.remap;
+    p.seg_w = pl.seg_w;
+    p.nt = pl.nt;
+    const dim3 grid(pl.grid), block(pl.block);
+    return with_dtype(pl.dtype, [&](auto tag) -> hipError_t {
         using T = decltype(tag);
-        constexpr uint32_t CW = kCascadeCols<T>;
-        constexpr uint32_t CN = CW / 2;
-        return with_method(method, [&](auto mtag) -> hipError_t {
-            constexpr int M = decltype(mtag)::value;
-            auto go_m = [&](auto ctag, auto nttag, auto mdtag) {
-                constexpr int C = decltype(ctag)::value;
-                constexpr bool NT = decltype(nttag)::value;
-                constexpr int MD = decltype(mdtag)::value;
-                if (launch_log_on())
-                    launch_log_record(
-                      "family=tiled dtype=%d method=%d n_out=%d grid=%u block=%u units=%u "
-                      "units_x=%u cols=%d nt=%d remap=%u seg_w=%u wpb=%u zwaves=%u nested=%d "
-                      "main_blocks=%u",
-                      int(sizeof(T)), M, std::min(n_out, 4), grid, 64 * wpb, p.total_units,
-                      p.units_x, C, int(NT), p.remap, p.seg_w, wpb, p.zwaves, int(MD == 1),
-                      p.main_blocks);
-                switch (n_out) {
-                    case 1:
-                        hipLaunchKernelGGL((cascade_kernel<T, M, 1, C, NT, MD>), dim3(grid),
-                                           dim3(64 * wpb), 0, stream, p);
-                        break;
-                    case 2:
-                        hipLaunchKernelGGL((cascade_kernel<T, M, 2, C, NT, MD>), dim3(grid),
-                                           dim3(64 * wpb), 0, stream, p);
-                        break;
-                    case 3:
-                        hipLaunchKernelGGL((cascade_kernel<T, M, 3, C, NT, MD>), dim3(grid),
-                                           dim3(64 * wpb), 0, stream, p);
-                        break;
-                    default:
-                        hipLaunchKernelGGL((cascade_kernel<T, M, 4, C, NT, MD>), dim3(grid),
-                                           dim3(64 * wpb), 0, stream, p);
-                        break;
-                }
-            };
-            auto go = [&](auto ctag, auto nttag) {
-                if (nested)
-                    go_m(ctag, nttag, std::integral_constant<int, 1>{});
-                else
-                    go_m(ctag, nttag, std::integral_constant<int, 2>{});
-            };
-            auto go_c = [&](auto nttag) {
-                if (cols == CW)
-                    go(std::integral_constant<int, int(CW)>{}, nttag);
-                else
-                    go(std::integral_constant<int, int(CN)>{}, nttag);
-            };
-            if (p.nt)
-                go_c(std::true_type{});
-            else
-                go_c(std::false_type{});
+        constexpr int CW = kCascadeCols<T>;
+        constexpr int CN = CW / 2;
+        auto go = [&](auto mtag, auto ltag, auto nttag, auto ctag, auto mdtag) -> hipError_t {
+            hipLaunchKernelGGL((cascade_kernel<T, decltype(mtag)::value, decltype(ltag)::value,
+                                               decltype(ctag)::value, decltype(nttag)::value,
+                                               decltype(mdtag)::value>),
+                               grid, block, 0, stream, p);
             return hipGetLastError();
+        };
+        return with_method(pl.method, [&](auto mtag) -> hipError_t {
+            return with_levels(pl.n_out, [&](auto ltag) -> hipError_t {
+                return with_flag(pl.nt != 0, [&](auto nttag) -> hipError_t {
+                    // tiled mode 1: wave blocks and tiles nest; 2: they do not
+                    auto go_c = [&](auto ctag) -> hipError_t {
+                        return pl.nested ? go(mtag, ltag, nttag, ctag, int_tag<1>{})
+                                         : go(mtag, ltag, nttag, ctag, int_tag<2>{});
+                    };
+                    if (pl.cols == uint32_t(CW))
+                        return go_c(int_tag<CW>{});
+                    if (pl.cols == uint32_t(CN))
+                        return go_c(int_tag<CN>{});
+                    return hipErrorInvalidValue;
+                });
+            });
         });
     });
 }
-#if AQZ_SHARD == 0
-
-bool
-volume_supported(int dtype,
-                 const void* src,
-                 uint32_t W,
-                 uint32_t H,
-                 const LevelOut* outs,
-                 int n_out)
-{
-    return n_out >= 1 && n_out <= kMaxVolumeLevels &&
-           cascade_fits(dtype_bytes(dtype), src, uint64_t(W) * H, W, H, outs, n_out,
-                        cascade_cols(dtype_bytes(dtype)));
-}
-#endif
 
 hipError_t
-AQZ_SHARDED(launch_volume)(int dtype,
-              int method,
-              const void* src,
-              uint64_t src_frame_elems,
-              uint32_t W,
-              uint32_t H,
-              const LevelOut* outs,
-              int n_out,
-              uint32_t n_planes,
-              hipStream_t stream)
+AQZ_SHARDED(run_volume)(const VolumePlan& pl, const void* src, uint64_t src_frame_elems,
+                        uint32_t W, uint32_t H, const LevelOut* outs, hipStream_t stream)
 {
-    if (!volume_supported(dtype, src, W, H, outs, n_out) || n_planes == 0 ||
-        n_planes % (1u << n_out) != 0)
+    if (!pl.valid)
         return hipErrorInvalidValue;
-    return with_dtype(dtype, [&](auto tag) -> hipError_t {
+    VolumeParams p{};
+    fill_frames(p, pl, src, src_frame_elems, W, H, outs);
+    const dim3 grid(pl.grid), block(pl.block);
+    return with_dtype(pl.dtype, [&](auto tag) -> hipError_t {
         using T = decltype(tag);
-        constexpr uint32_t C = 16 / sizeof(T);
-        VolumeParams p{};
-        p.src = static_cast<const uint8_t*>(src);
-        p.src_frame_elems = src_frame_elems;
-        p.W = W;
-        p.H = H;
-        const uint32_t R = 1u << n_out;
-        p.units_x = (W + 64 * C - 1) / (64 * C);
-        p.units_y = (H + R - 1) / R;
-        const uint64_t total =
-          uint64_t(p.units_x) * p.units_y * (n_planes >> n_out);
-        if (total >= (1ull << 31))
-            return hipErrorInvalidValue;
-        p.total_units = uint32_t(total);
-        for (int i = 0; i < n_out; ++i) {
-            p.dst[i] = static_cast<uint8_t*>(outs[i].ptr);
-            p.dst_frame_elems[i] = outs[i].frame_elems;
-            p.w[i] = outs[i].w;
-            p.h[i] = outs[i].h;
-        }
-        // Load policy and units per wave: with the
-        // volume in HBM (rotating buffer sets) nontemporal loads beat plain
-        // ones for every method, Decimate's every-other-row, every-other-
-        // plane reads included (44.0-44.4 against 46.7-47.4 us); Decimate's
-        // 4-KiB units go two to a wave (one ties).  The plain-load choice of
-        // §11.2 had been timed with Decimate's 128 MiB read set resident in
-        // the Infinity Cache.  $AQZ_VOLUME_NT=0/1 and $AQZ_VOLUME_UPW=1/2
-        // (Decimate) override.
-        static const int nt_env = int_env("AQZ_VOLUME_NT", -1);
-        static const int upw_env = int_env("AQZ_VOLUME_UPW", 0);
-        return with_method(method, [&](auto mtag) -> hipError_t {
+        constexpr int CZ = 16 / int(sizeof(T));
+        return with_method(pl.method, [&](auto mtag) -> hipError_t {
             constexpr int M = decltype(mtag)::value;
-            const bool ntl = nt_env >= 0 ? nt_env != 0 : true;
-            // $AQZ_VOLUME_UPW=4 (A/B, Decimate): four units per wave, 16 KiB
-            // of loads in flight per wave.  Only the nontemporal-load kernels
-            // are built for four, so with plain loads ($AQZ_VOLUME_NT=0) the
-            // request is clamped to two.  (Until round 6 the grid was sized
-            // for four while the one-unit kernel ran, which left three
-            // quarters of the units unwritten.)  Every launch below sizes its
-            // grid from the UPW its kernel is instantiated with.
-            const int upw = M == kDecimate ? (upw_env >= 4 ? (ntl ? 4 : 2)
-                                              : upw_env > 0 ? std::min(upw_env, 2) : 2)
-                                           : 1;
-            auto vol_launch = [&](auto nltag, auto ntltag, auto upwtag, auto zftag) {
-                constexpr int NLK = decltype(nltag)::value;
-                constexpr bool NTL = decltype(ntltag)::value;
-                constexpr int UPW = decltype(upwtag)::value;
-                constexpr bool ZF = decltype(zftag)::value;
-                constexpr int CZ = 16 / int(sizeof(T));
-                const uint32_t grid = grid_for((total + UPW - 1) / UPW, 4, 0);
-                if (launch_log_on())
-                    launch_log_record(
-                      "family=volume dtype=%d method=%d n_out=%d grid=%u block=256 units=%u "
-                      "units_x=%u upw=%d ntl=%d zfast=%d UPW=%d",
-                      int(sizeof(T)), M, NLK, grid, p.total_units, p.units_x, upw, int(NTL),
-                      int(ZF), UPW);
-                hipLaunchKernelGGL((volume_kernel<T, M, NLK, NTL, UPW, CZ, ZF>), dim3(grid),
-                                   dim3(256), 0, stream, p);
+            auto go = [&](auto nltag) -> hipError_t {
+                auto run = [&](auto ntltag, auto upwtag, auto zftag) -> hipError_t {
+                    hipLaunchKernelGGL((volume_kernel<T, M, decltype(nltag)::value,
+                                                      decltype(ntltag)::value,
+                                                      decltype(upwtag)::value, CZ,
+                                                      decltype(zftag)::value>),
+                                       grid, block, 0, stream, p);
+                    return hipGetLastError();
+                };
+                // Decimate alone has kernels of two and four units per wave;
+                // four, and the plane-groups-fastest order, only with
+                // nontemporal loads
+                if constexpr (M == kDecimate) {
+                    if (pl.upw == 4 && pl.ntl)
+                        return with_flag(pl.zfast, [&](auto zftag) -> hipError_t {
+                            return run(std::true_type{}, int_tag<4>{}, zftag);
+                        });
+                    if (pl.upw == 2 && pl.zfast && pl.ntl)
+                        return run(std::true_type{}, int_tag<2>{}, std::true_type{});
+                    if (pl.upw == 2 && !pl.zfast)
+                        return with_flag(pl.ntl, [&](auto ntltag) -> hipError_t {
+                            return run(ntltag, int_tag<2>{}, std::false_type{});
+                        });
+                }
+                if (pl.upw != 1 || pl.zfast)
+                    return hipErrorInvalidValue;
+                return with_flag(pl.ntl, [&](auto ntltag) -> hipError_t {
+                    return run(ntltag, int_tag<1>{}, std::false_type{});
+                });
             };
-#define AQZ_VOL_Z(NL, NTL, UPW, ZF)                                                       \
-    vol_launch(std::integral_constant<int, NL>{}, std::integral_constant<bool, NTL>{},    \
-               std::integral_constant<int, UPW>{}, std::integral_constant<bool, ZF>{})
-#define AQZ_VOL(NL, NTL, UPW) AQZ_VOL_Z(NL, NTL, UPW, false)
-            // Decimate launches of 128 or more plane groups (two or more
-            // config-V volumes) take the plane groups fastest in the unit
-            // order, so the units in flight spread over many planes: four
-            // 1024^2 x 256 volumes 172.1-172.3 -> 148.1-149.0 us, data in HBM
-            // (profiles/r05/vzfast/ab.log); one volume (64 groups) loses
-            // 1-2% that way and keeps columns fastest.  Its reads never set
-            // the address bits of odd rows and odd planes.
-            // $AQZ_VOLUME_ZFAST=0 / 1: never / always (nontemporal loads).
-            static const int zf_env = int_env("AQZ_VOLUME_ZFAST", -1);
-            const bool zfast = zf_env >= 0 ? zf_env != 0 : (n_planes >> n_out) >= 128;
-            if constexpr (M == kDecimate) {
-                if (upw == 4 && ntl) {
-                    if (zfast && n_out == 1)
-                        AQZ_VOL_Z(1, true, 4, true);
-                    else if (zfast)
-                        AQZ_VOL_Z(2, true, 4, true);
-                    else if (n_out == 1)
-                        AQZ_VOL(1, true, 4);
-                    else
-                        AQZ_VOL(2, true, 4);
-                    return hipGetLastError();
-                }
-                if (upw == 2 && zfast && ntl) {
-                    if (n_out == 1)
-                        AQZ_VOL_Z(1, true, 2, true);
-                    else
-                        AQZ_VOL_Z(2, true, 2, true);
-                    return hipGetLastError();
-                }
-                if (upw == 2) {
-                    if (n_out == 1 && ntl)
-                        AQZ_VOL(1, true, 2);
-                    else if (n_out == 1)
-                        AQZ_VOL(1, false, 2);
-                    else if (ntl)
-                        AQZ_VOL(2, true, 2);
-                    else
-                        AQZ_VOL(2, false, 2);
-                    return hipGetLastError();
-                }
-            }
-            if (n_out == 1 && ntl)
-                AQZ_VOL(1, true, 1);
-            else if (n_out == 1)
-                AQZ_VOL(1, false, 1);
-            else if (ntl)
-                AQZ_VOL(2, true, 1);
-            else
-                AQZ_VOL(2, false, 1);
-#undef AQZ_VOL
-#undef AQZ_VOL_Z
-            return hipGetLastError();
+            if (pl.n_out == 1)
+                return go(int_tag<1>{});
+            if (pl.n_out == 2)
+                return go(int_tag<2>{});
+            return hipErrorInvalidValue;
         });
     });
 }
-#if AQZ_SHARD == 0
-
-uint32_t
-tile_slices(uint32_t tile_rows, uint32_t tile_cols)
-{
-    // ~8 K elements per block, at most 64 blocks per tile
-    const uint64_t tile_elems = uint64_t(tile_rows) * tile_cols;
-    return uint32_t(std::min<uint64_t>(64, std::max<uint64_t>(1, tile_elems / 8192)));
-}
-#endif
 
 namespace {
 

@@ -1,0 +1,258 @@
+// ds_plan.hh — what launch_cascade, launch_cascade_tiled and launch_volume
+// launch: host-only integer arithmetic over the dtype size, method, geometry,
+// buffer alignment and the $AQZ_* A/B switches.  No HIP type appears here
+// (ds_plan.cpp builds with a plain C++ compiler; tests/cpp/plan_probe.cpp
+// runs it on the CPU).  ds_dispatch.cpp builds a plan per launch, logs
+// format_plan() of it and hands it to the dtype's kernel shard
+// (ds_kernels.hip), which maps the selector fields to template arguments and
+// takes grid, block and LDS from the plan as they stand.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <cstdlib>
+#include <functional>
+#include <string>
+
+namespace aqz {
+
+constexpr int kMaxFusedLevels = 4;
+constexpr int kMaxVolumeLevels = 2;
+
+enum
+{
+    kDecimate = 0,
+    kMean = 1,
+    kMin = 2,
+    kMax = 3
+};
+
+// One output level of a cascade launch.  `frame_elems` is the element stride
+// between consecutive frames of that level (w*h for densely packed batches).
+struct LevelOut
+{
+    void* ptr;
+    uint64_t frame_elems;
+    uint32_t w, h;
+};
+
+// Chunk-tiled output of one cascade level: frame k of
+// the level at ptr + k * n_tiles * tile_rows * tile_cols elements, tile
+// t = ty * n_tiles_x + tx holding tile_rows x tile_cols elements row-major,
+// zero where it overhangs the level — the layout Array::write_frame_to_chunks_
+// fills (array.cpp:507-622, chunk.cpp:17-58).  `nonzero` (optional, device)
+// receives the chunk zero scan as flag bytes (cascade_tiled_slots).
+// Chunk lattice instead (frame_offsets non-null, device): frame k's tile t at
+// ptr + frame_offsets[k] + t * tile_stride elements — every tile straight
+// into its chunk buffer at the frame's place in it.
+struct TiledOut
+{
+    void* ptr;
+    uint32_t tile_rows, tile_cols;
+    uint8_t* nonzero;
+    const uint64_t* frame_offsets = nullptr; // elements, n_frames entries
+    uint64_t tile_stride = 0;                // elements (with frame_offsets)
+};
+
+// The A/B switches of the three launchers, one field per $AQZ_* name, each
+// at its "unset" value.  Rationale and measurements stand where a switch is
+// used (ds_plan.cpp).
+struct LaunchSwitches
+{
+    // $AQZ_LOAD_NT: 1 / 0 forces the fused cascade's loads with / without the
+    // non-temporal hint (A/B only); unset (-1): the planner decides.
+    int load_nt = -1;
+    // $AQZ_STORE_WB: a level bit mask (bit J-1 = level J) of row-major stores
+    // issued write-back instead of non-temporal (A/B).
+    int store_wb = -1;
+    // $AQZ_SPLIT_LOADS: 1 / 0 = band kernels of 4- and 8-byte types load each
+    // row's 2 KiB wave segment as two contiguous halves (cascade_unit SPLIT)
+    // or as 32 bytes per lane.
+    bool split_loads = false;
+    // $AQZ_XCD_REMAP: unset = the default (off), 0 = off, 1 = on (A/B only).
+    int xcd_remap = -1;
+    // $AQZ_CASCADE_NARROW=0/1: wide / narrow tiles for 4- and 8-byte types.
+    int cascade_narrow = -1;
+    // $AQZ_CASCADE_WAVES (waves per workgroup, 4 = default, 1..8) and
+    // $AQZ_UNIT_ORDER (0 columns fastest = default, 1 frames fastest, 2 row
+    // bands fastest): the row-major cascade's unit-to-wave mapping.
+    uint32_t cascade_waves = 4;
+    uint32_t unit_order = 0;
+    // $AQZ_UNITS_PER_WAVE=k forces k (up to 16) units per cascade wave.
+    int units_per_wave = 0;
+    // $AQZ_BAND_STAGING=0: never stage a band in LDS.
+    bool band_off = false;
+    // $AQZ_BAND_LAST=K forces the last K (up to 8) waves to store every band
+    // (0: the barrier).
+    int band_last = -1;
+    // $AQZ_BAND_MIS_MAX: the widest misaligned band staged whole (up to 8).
+    int band_mis_max = -1;
+    // $AQZ_BAND_MIS_SEG: misaligned bands wider than one wave may store go in
+    // rowwise segments of that many tiles (up to 8); 0: never.
+    int band_mis_seg = -1;
+    // $AQZ_BAND_FORCE stages a level mask whatever the alignment, in bands of
+    // up to 8 waves.
+    uint32_t band_force = 0;
+    // $AQZ_BAND_ALIGNED=0: aligned frames keep direct stores.
+    bool band_aligned = true;
+    // $AQZ_BAND_SEGMENTS=0: no 8-tile segments of aligned bands wider than 8.
+    bool band_segments = true;
+    // $AQZ_BAND_SEG4=0 / 1: aligned bands never / always go in segments.
+    int band_seg4 = -1;
+    // $AQZ_BAND_SEGN: tiles per such segment (up to 8).
+    int band_segn = 0;
+    // $AQZ_BAND_WG=0: no band workgroups for direct stores of split bursts.
+    bool band_wg = true;
+    // $AQZ_BAND_LDS_CAP (bytes) lowers the device's LDS cap.
+    int band_lds_cap = 0;
+    // $AQZ_TILED_NARROW: 1 half-width tiles wherever they fit, 0 wide
+    // (cascade_tiled_cols).
+    int tiled_narrow = -1;
+    // $AQZ_TILED_ZWAVES: unset = the planner's count of zero-fill waves, else
+    // that count (0 skips the zero fill and leaves the overhang unwritten).
+    int tiled_zwaves = -1;
+    // $AQZ_TILED_ZROWS_PER_WAVE: overhang rows per zero-fill wave for every
+    // type (0: the byte rule alone).
+    int tiled_zrows_per_wave = -1;
+    // $AQZ_TILED_BAND_WG=1: one workgroup per row band on rows that split
+    // 128-B lines (off by default).
+    bool tiled_band_wg = false;
+    // $AQZ_TILED_WAVES (1..8) forces the waves per workgroup.
+    int tiled_waves = 0;
+    // $AQZ_VOLUME_NT=0/1, $AQZ_VOLUME_UPW=1/2/4 (Decimate) and
+    // $AQZ_VOLUME_ZFAST=0 / 1 (never / always, nontemporal loads).
+    int volume_nt = -1;
+    int volume_upw = 0;
+    int volume_zfast = -1;
+
+    // `get(name)`: the switch's text, or null when unset.
+    static LaunchSwitches from(const std::function<const char*(const char*)>& get);
+    static LaunchSwitches from_env()
+    {
+        return from([](const char* name) -> const char* { return std::getenv(name); });
+    }
+};
+
+// The process-wide instance the library plans with: read from the
+// environment on first use, once per process.
+const LaunchSwitches& launch_switches();
+
+size_t dtype_bytes(int dtype);
+inline bool dtype_valid(int dtype) { return dtype_bytes(dtype) != 0; }
+inline bool method_valid(int method) { return method >= kDecimate && method <= kMax; }
+
+uint32_t grid_for(uint64_t work_items, uint32_t per_block, uint32_t cap);
+
+// Columns per lane the fused cascade would use for this run of levels (0:
+// unsupported).  Any width and byte offset works as long as the buffers are
+// element-aligned, a row holds at least one 16-byte (narrow tiles: 8-byte)
+// load, and each output level is exactly ceil(in/2) of the one before.
+uint32_t cascade_pick_cols(int dtype, const void* src, uint64_t src_frame_elems, uint32_t W,
+                           uint32_t H, const LevelOut* outs, int n_out,
+                           const LaunchSwitches& sw = launch_switches());
+inline bool
+cascade_supported(int dtype, const void* src, uint64_t src_frame_elems, uint32_t W, uint32_t H,
+                  const LevelOut* outs, int n_out)
+{
+    return cascade_pick_cols(dtype, src, src_frame_elems, W, H, outs, n_out) != 0;
+}
+
+// Columns per lane launch_cascade_tiled uses for W-wide frames of `dtype`
+// (cascade_pick_cols for element-aligned buffers).
+uint32_t cascade_tiled_cols(int dtype, uint32_t W, const LaunchSwitches& sw = launch_switches());
+
+// Zero-scan flag bytes per tile that launch_cascade_tiled writes for level
+// `level` (1-based within a launch of n_out levels over W-wide frames): when
+// the kernel's wave blocks tile the chunk tiles exactly, `slots` bytes per
+// tile (*slots_x across), each written once by the wave owning that block —
+// the tile is nonzero iff any of its slots is; returns 0 otherwise (one byte
+// per tile, cleared before the launch).
+uint32_t cascade_tiled_slots(int dtype, uint32_t W, int n_out, int level, uint32_t tile_rows,
+                             uint32_t tile_cols, uint32_t* slots_x,
+                             const LaunchSwitches& sw = launch_switches());
+
+bool volume_supported(int dtype, const void* src, uint32_t W, uint32_t H, const LevelOut* outs,
+                      int n_out);
+
+// Slices per tile of launch_tile_frame_sliced.
+uint32_t tile_slices(uint32_t tile_rows, uint32_t tile_cols);
+
+// ---- plans ------------------------------------------------------------------
+// A plan is a pure function of its arguments.  `valid` is false for exactly
+// the inputs the launcher answers with hipErrorInvalidValue.  Selector fields
+// choose the kernel instantiation; grid / block / lds are the launch shape;
+// the rest are the scalars of CascadeParams / VolumeParams.
+
+struct CascadePlan
+{
+    bool valid = false;
+    int dtype = 0, method = 0, n_out = 0;
+    uint32_t bytes = 0; // dtype size
+    // selectors: cascade_kernel<T, M, n_out, cols, nt>, or with `band`
+    // cascade_band_kernel<T, M, n_out, cols, nt, seg_rowwise, split>
+    uint32_t cols = 0, nt = 0;
+    bool band = false, split = false;
+    uint32_t grid = 0, block = 0, lds = 0;
+    uint32_t units_x = 0, units_y = 0, total_units = 0;
+    uint32_t upw = 1, main_blocks = 0, order = 0, remap = 0, wb = 0;
+    uint32_t seg_w = 0, band_last = 0, seg_rowwise = 0;
+    uint32_t stage_mask = 0, seg_tiles = 0; // band kernel arguments
+};
+
+struct TiledLevelPlan
+{
+    uint32_t ntx = 0, nty = 0, pw = 0, ph = 0;
+    uint64_t tframe_elems = 0, tstride = 0;
+    uint32_t cov_w = 0, cov_h = 0, zrows = 0;
+    uint32_t slots = 0, slots_x = 1, flags_frame = 0;
+    // one flag per tile, OR-ed by plain stores of 1: the launcher clears
+    // n_frames * ntx * nty flag bytes first
+    bool clear_flags = false;
+};
+
+struct TiledPlan
+{
+    bool valid = false;
+    int dtype = 0, method = 0, n_out = 0;
+    uint32_t bytes = 0;
+    // selectors: cascade_kernel<T, M, n_out, cols, nt, nested ? 1 : 2>
+    uint32_t cols = 0, nt = 0;
+    bool nested = true; // every level's wave blocks and tiles nest
+    uint32_t grid = 0, block = 0, wpb = 0;
+    uint32_t n_frames = 0;
+    uint32_t units_x = 0, units_y = 0, total_units = 0;
+    uint32_t zitems = 0, zwaves = 0, main_blocks = 0, remap = 0, seg_w = 0;
+    TiledLevelPlan lv[kMaxFusedLevels];
+};
+
+struct VolumePlan
+{
+    bool valid = false;
+    int dtype = 0, method = 0, n_out = 0;
+    uint32_t bytes = 0;
+    // selectors: volume_kernel<T, M, n_out, ntl, upw, 16 / bytes, zfast>
+    bool ntl = true, zfast = false;
+    int upw = 1;
+    uint32_t grid = 0, block = 256;
+    uint32_t units_x = 0, units_y = 0, total_units = 0;
+};
+
+// `lds_cap`: the device's LDS per workgroup, less the band kernel's static
+// arrival counter (ds_dispatch.cpp asks the device once).
+CascadePlan plan_cascade(int dtype, int method, const void* src, uint64_t src_frame_elems,
+                         uint32_t W, uint32_t H, const LevelOut* outs, int n_out,
+                         uint32_t n_frames, uint32_t lds_cap, const LaunchSwitches& sw);
+TiledPlan plan_cascade_tiled(int dtype, int method, const void* src, uint64_t src_frame_elems,
+                             uint32_t W, uint32_t H, const LevelOut* outs, const TiledOut* touts,
+                             int n_out, uint32_t n_frames, const LaunchSwitches& sw);
+VolumePlan plan_volume(int dtype, int method, const void* src, uint64_t src_frame_elems,
+                       uint32_t W, uint32_t H, const LevelOut* outs, int n_out,
+                       uint32_t n_planes, const LaunchSwitches& sw);
+
+// The launch log's line (launch_log.hh) for a valid plan: family=cascade or
+// family=band, family=tiled, family=volume.
+std::string format_plan(const CascadePlan& p);
+std::string format_plan(const TiledPlan& p);
+std::string format_plan(const VolumePlan& p);
+
+} // namespace aqz

@@ -16,20 +16,20 @@ HIPCC=/opt/rocm/bin/hipcc
 HF="-O1 -g -std=c++20 -fPIC --offload-arch=gfx950 -I$ROOT/include -I$ROOT/acquire-zarr_amd/csrc"
 HS="-Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-omit-frame-pointer"
 # ds_kernels.hip in the library's 8 dtype shards, in parallel (ds_dispatch.cpp
-# routes the launchers), like acquire-zarr_amd/Makefile
+# plans with ds_plan.cpp and routes the launchers), like acquire-zarr_amd/Makefile
 pids=()
 for k in 0 1 2 3 4 5 6 7; do
   $HIPCC $HF $HS -DAQZ_SHARDS=8 -DAQZ_SHARD=$k -x hip -c "$ROOT/acquire-zarr_amd/csrc/ds_kernels.hip" \
       -o "$OUT/ds_kernels_s$k.o" &
   pids+=($!)
 done
-for f in ds_dispatch.cpp ds_runtime.cpp ds_node.cpp codec_runtime.cpp blosc_frame.cpp launch_log.cpp; do
+for f in ds_plan.cpp ds_dispatch.cpp ds_runtime.cpp ds_node.cpp codec_runtime.cpp blosc_frame.cpp launch_log.cpp; do
   $HIPCC $HF $HS -DAQZ_SHARDS=8 -x hip -c "$ROOT/acquire-zarr_amd/csrc/$f" -o "$OUT/${f%.*}.o"
 done
 $HIPCC $HF $HS -c "$ROOT/acquire-zarr_amd/csrc/codec_kernels.hip" -o "$OUT/codec_kernels.o"
 for p in "${pids[@]}"; do wait "$p"; done
 $HIPCC --offload-arch=gfx950 -shared -fPIC -fsanitize=address,undefined \
-    "$OUT"/ds_kernels_s?.o "$OUT/ds_dispatch.o" "$OUT/ds_runtime.o" "$OUT/ds_node.o" "$OUT/codec_runtime.o" \
+    "$OUT"/ds_kernels_s?.o "$OUT/ds_plan.o" "$OUT/ds_dispatch.o" "$OUT/ds_runtime.o" "$OUT/ds_node.o" "$OUT/codec_runtime.o" \
     "$OUT/codec_kernels.o" "$OUT/blosc_frame.o" "$OUT/launch_log.o" -o "$OUT/libaqz_san.so" \
     -Wl,-rpath,/opt/rocm/lib -ldl -lpthread
 # the driver must use the same (clang) sanitizer runtime as the library

@@ -1,7 +1,8 @@
 """Runner for tests/test_gpu_launch_rules.py (not a test module).
 
-The launchers read their A/B switches ($AQZ_*) once per process, into static
-locals, so every launch rule runs in a process of its own: the test starts
+The launchers read their A/B switches ($AQZ_*) once per process (the
+process-wide LaunchSwitches, ds_plan.hh), so every launch rule runs in a
+process of its own: the test starts
 this file (a new process, never exec'd) with one rule's environment plus
 AQZ_LAUNCH_LOG=1.
 
@@ -70,7 +71,7 @@ EXTRA_FILTER_CASES = [
     (1, 4096, 4096 * 5, 2),
 ]
 # LDS a workgroup may use on gfx950, less the band kernel's arrival counter
-# (band_lds_cap, ds_kernels.hip)
+# (device_lds_cap, ds_dispatch.cpp)
 LDS_MAX = 160 * 1024 - 16
 
 

@@ -3,7 +3,7 @@ scheme each fixed geometry takes under the default launch.
 
 The library ships many kernel instantiations the default launch never
 reaches, selected by the $AQZ_* switches that launch_cascade,
-launch_cascade_tiled and launch_volume (csrc/ds_kernels.hip) and the blosc
+launch_cascade_tiled and launch_volume (planned in csrc/ds_plan.cpp) and the blosc
 filter dispatch (csrc/codec_kernels.hip) read.  Each is one default flip away
 from being the product, so each rule of RULES below runs its family's case
 list (tests/launch_rule_child.py: the smallest shapes at which each store
@@ -24,7 +24,8 @@ without its fixed case.
 Values outside what the launcher's comments document are not run;
 AQZ_TILED_ZWAVES=0 is documented to leave the tile overhang unwritten.
 tests/test_launch_rules_table.py (CPU) checks that every switch the sources
-read is in RULES or exempt for a stated reason.
+read is in RULES or exempt for a stated reason; tests/test_launch_plan.py
+(CPU) asserts the pins and proofs below on the planner's own output.
 """
 import json
 import os

@@ -12,6 +12,9 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++20 -I include
 //          -I acquire-zarr_amd/csrc tools/cascade_ablate.hip -o tools/cascade_ablate
 #include "../acquire-zarr_amd/csrc/ds_kernels.hip"
+// the launchers' host side: the planner and the (here unsharded) entry points
+#include "../acquire-zarr_amd/csrc/ds_plan.cpp"
+#include "../acquire-zarr_amd/csrc/ds_dispatch.cpp"
 
 #include <algorithm>
 #include <cstdio>

@@ -11,6 +11,9 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++20 -I include
 //          -I acquire-zarr_amd/csrc tools/microbench.hip -o tools/microbench
 #include "../acquire-zarr_amd/csrc/ds_kernels.hip"
+// the launchers' host side: the planner and the (here unsharded) entry points
+#include "../acquire-zarr_amd/csrc/ds_plan.cpp"
+#include "../acquire-zarr_amd/csrc/ds_dispatch.cpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -449,9 +452,9 @@ run_volume(uint32_t planes, int reps)
                                              dim3(256), 0, 0, p);
                       }, {} });
     };
-    add("volume C16", volume_kernel<uint16_t, kMean, 2, 16, false>, 16);
-    add("volume C8 zfast", volume_kernel<uint16_t, kMean, 2, 8, true>, 8);
-    add("volume C16 zfast", volume_kernel<uint16_t, kMean, 2, 16, true>, 16);
+    add("volume C16", volume_kernel<uint16_t, kMean, 2, true, 1, 16, false>, 16);
+    add("volume C8 zfast", volume_kernel<uint16_t, kMean, 2, true, 1, 8, true>, 8);
+    add("volume C16 zfast", volume_kernel<uint16_t, kMean, 2, true, 1, 16, true>, 16);
     vs.push_back({ "read (volume, nt)", [&] {
                       hipLaunchKernelGGL(read_kernel, dim3(4096), dim3(256), 0, 0,
                                          reinterpret_cast<const u32x4*>(d_in),

@@ -16,6 +16,9 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++20 -I include
 //          -I acquire-zarr_amd/csrc tools/variants.hip -o tools/variants
 #include "../acquire-zarr_amd/csrc/ds_kernels.hip"
+// the launchers' host side: the planner and the (here unsharded) entry points
+#include "../acquire-zarr_amd/csrc/ds_plan.cpp"
+#include "../acquire-zarr_amd/csrc/ds_dispatch.cpp"
 #include "aqz_downsampler.h"
 
 #include <algorithm>
