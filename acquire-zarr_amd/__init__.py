@@ -45,6 +45,8 @@ EXPORTS = (
     "aqz_ds_run_device_batch_chunked", "aqz_chunk_frame_offsets",
     "aqz_blosc_blocksize", "aqz_blosc_frame_from_filtered", "aqz_blosc_ctx_create",
     "aqz_blosc_ctx_destroy", "aqz_blosc_compress_device", "aqz_blosc_codec_info",
+    "aqz_blosc_lz4_frames_device", "aqz_blosc_lz4_compress_device",
+    "aqz_debug_blosc_d2h_bytes", "aqz_debug_lz4_block_host",
     "aqz_ds_level_bytes", "aqz_ds_level_count", "aqz_ds_device_memory_usage",
     "aqz_ds_device",
     "aqz_ds_last_error", "aqz_last_error", "aqz_method_name",
@@ -156,6 +158,13 @@ def lib() -> ctypes.CDLL:
     L.aqz_blosc_compress_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, u32,
                                             ctypes.c_char_p, vp, sz, u32, vp, sz,
                                             ctypes.POINTER(sz), vp]
+    L.aqz_blosc_lz4_frames_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, u32, vp, sz, u32,
+                                              vp, sz, vp, vp, u32]
+    L.aqz_blosc_lz4_compress_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, u32, vp, sz, u32,
+                                                vp, sz, ctypes.POINTER(sz), vp, u32]
+    L.aqz_debug_blosc_d2h_bytes.argtypes = [vp]
+    L.aqz_debug_blosc_d2h_bytes.restype = ctypes.c_uint64
+    L.aqz_debug_lz4_block_host.argtypes = [vp, sz, vp, sz, ctypes.c_int, ctypes.POINTER(u32)]
     L.aqz_blosc_codec_info.argtypes = []
     L.aqz_blosc_codec_info.restype = ctypes.c_char_p
     L.aqz_ds_add_device_frame.argtypes = [vp, vp, sz]
@@ -727,6 +736,53 @@ class BloscContext:
         if not own:
             return list(sizes)
         return [host_dst[k * stride:k * stride + sizes[k]].tobytes() for k in range(n_buffers)]
+
+
+    def lz4_frames_device(self, clevel: int, shuffle: int, typesize: int, device_src: int,
+                          nbytes: int, n_buffers: int, device_dst: int, dst_stride: int,
+                          device_frame_bytes: int, stream: int = 0, flags: int = 0):
+        """aqz_blosc_lz4_frames_device: filter, LZ4 and frame layout on the
+        device, asynchronous on `stream`; frame k at device_dst + k * dst_stride,
+        its size in the device uint32 array `device_frame_bytes`."""
+        _raise_if(lib().aqz_blosc_lz4_frames_device(
+            self._h, clevel, shuffle, typesize, device_src, nbytes, n_buffers, device_dst,
+            dst_stride, device_frame_bytes, ctypes.c_void_p(stream) if stream else None, flags))
+
+    def lz4_compress_device(self, clevel: int, shuffle: int, typesize: int, device_src: int,
+                            nbytes: int, n_buffers: int, stream: int = 0, host_dst=None,
+                            dst_stride: int = 0, flags: int = 0):
+        """aqz_blosc_lz4_compress_device, mirroring compress_device (lz4 only):
+        the list of frames (bytes) when `host_dst` is None, else the sizes."""
+        stride = dst_stride or nbytes + BLOSC_MAX_OVERHEAD
+        own = host_dst is None
+        if own:
+            host_dst = np.empty(n_buffers * stride, np.uint8)
+        sizes = (ctypes.c_size_t * n_buffers)()
+        _raise_if(lib().aqz_blosc_lz4_compress_device(
+            self._h, clevel, shuffle, typesize, device_src, nbytes, n_buffers,
+            host_dst.ctypes.data, stride, sizes,
+            ctypes.c_void_p(stream) if stream else None, flags))
+        if not own:
+            return list(sizes)
+        return [host_dst[k * stride:k * stride + sizes[k]].tobytes() for k in range(n_buffers)]
+
+    def d2h_bytes(self) -> int:
+        """Bytes the last lz4_compress_device copied from device to host."""
+        return lib().aqz_debug_blosc_d2h_bytes(self._h)
+
+
+LZ4_PROBE_SERIAL = 1  # aqz_blosc.h
+
+
+def debug_lz4_block_host(src, cap: int, accel: int):
+    """aqz_debug_lz4_block_host: (return value, output bytes, need) of the
+    serial LZ4 block encoder on a host array; no GPU involved."""
+    s = np.ascontiguousarray(src).view(np.uint8).reshape(-1)
+    dst = np.zeros(max(cap, 1), np.uint8)
+    need = ctypes.c_uint32()
+    n = lib().aqz_debug_lz4_block_host(s.ctypes.data if s.size else None, s.size,
+                                       dst.ctypes.data, cap, accel, ctypes.byref(need))
+    return n, dst[:max(n, 0)].tobytes(), need.value
 
 
 def blosc_codec_info() -> str:

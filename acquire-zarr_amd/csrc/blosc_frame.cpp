@@ -28,6 +28,7 @@
 #include "aqz_blosc.h"
 #include "abi_guard.hh"
 #include "codec_kernels.hh"
+#include "lz4_block.hh"
 
 #include <hip/hip_runtime.h>
 
@@ -335,6 +336,20 @@ struct aqz_blosc_ctx
     uint8_t* h_filtered = nullptr; // pinned
     size_t h_cap = 0;
     std::vector<hipEvent_t> events; // one per D2H group
+    // aqz_blosc_lz4_frames_device / aqz_blosc_lz4_compress_device
+    void* d_comp = nullptr; // per-split LZ4 slots; afterwards the packed frames
+    size_t comp_cap = 0;
+    void* d_rows = nullptr; // (csize, need) per split
+    size_t rows_cap = 0;
+    void* d_frames = nullptr; // strided frames of the host-delivering call
+    size_t frames_cap = 0;
+    void* d_table = nullptr; // frame sizes (uint32) and pack offsets (uint64)
+    size_t table_cap = 0;
+    uint8_t* h_packed = nullptr; // pinned
+    size_t h_packed_cap = 0;
+    uint8_t* h_table = nullptr; // pinned: sizes, then offsets
+    size_t h_table_cap = 0;
+    uint64_t d2h_bytes = 0; // of the last aqz_blosc_lz4_compress_device
 };
 
 namespace {
@@ -352,6 +367,18 @@ release(aqz_blosc_ctx* c)
     c->d_filtered = nullptr;
     c->h_filtered = nullptr;
     c->d_cap = c->h_cap = 0;
+    for (void** p : { &c->d_comp, &c->d_rows, &c->d_frames, &c->d_table }) {
+        if (*p)
+            (void)hipFree(*p);
+        *p = nullptr;
+    }
+    for (uint8_t** p : { &c->h_packed, &c->h_table }) {
+        if (*p)
+            (void)hipHostFree(*p);
+        *p = nullptr;
+    }
+    c->comp_cap = c->rows_cap = c->frames_cap = c->table_cap = 0;
+    c->h_packed_cap = c->h_table_cap = 0;
 }
 
 int
@@ -383,9 +410,245 @@ copy_raw(const uint8_t* d_src, size_t nbytes, uint8_t* host_dst, size_t stride,
     return AQZ_OK;
 }
 
+// ---- blosc+LZ4 frames made on the device ------------------------------------
+
+int
+grow_device(void** p, size_t* cap, size_t want)
+{
+    if (*cap >= want)
+        return AQZ_OK;
+    if (*p)
+        BLOSC_HIP(hipFree(*p), "free");
+    *p = nullptr;
+    *cap = 0;
+    BLOSC_HIP(hipMalloc(p, want), "device scratch");
+    *cap = want;
+    return AQZ_OK;
+}
+
+int
+grow_pinned(uint8_t** p, size_t* cap, size_t want)
+{
+    if (*cap >= want)
+        return AQZ_OK;
+    if (*p)
+        BLOSC_HIP(hipHostFree(*p), "free pinned");
+    *p = nullptr;
+    *cap = 0;
+    BLOSC_HIP(hipHostMalloc(reinterpret_cast<void**>(p), want), "pinned staging");
+    *cap = want;
+    return AQZ_OK;
+}
+
+// Shared argument check of the two lz4 entry points (`dst` and `sizes` are
+// device or host pointers by the caller's contract; only null is caught).
+int
+check_lz4_call(const aqz_blosc_ctx* ctx, int clevel, int shuffle, uint32_t typesize,
+               const void* device_src, size_t nbytes, uint32_t n_buffers, const void* dst,
+               size_t dst_stride, const void* sizes, uint32_t flags, Params* p)
+{
+    if (!ctx || !device_src || !dst || !sizes || n_buffers == 0 || nbytes == 0 ||
+        nbytes > kMaxBuffer || dst_stride < nbytes + kHeader ||
+        (flags & ~uint32_t(AQZ_LZ4_PROBE_SERIAL)) != 0) {
+        aqz::set_last_error("blosc_lz4: invalid argument");
+        return AQZ_INVALID_ARGUMENT;
+    }
+    return check_params(clevel, shuffle, typesize, "lz4", p);
+}
+
+// filter -> LZ4 per split -> frames, all queued on `stream`; the device is
+// already current.
+int
+queue_lz4_frames(aqz_blosc_ctx* ctx, const Params& p, const uint8_t* src, size_t nbytes,
+                 uint32_t n_buffers, uint8_t* d_dst, size_t dst_stride, uint32_t* d_sizes,
+                 hipStream_t stream, uint32_t flags)
+{
+    const size_t bs = compute_blocksize(p, nbytes);
+    const bool memcpy_only = p.clevel == 0 || nbytes < kMinBuffer;
+    const uint32_t nsplits = split_block(p.codec, p.typesize, bs) ? p.typesize : 1u;
+    aqz::BloscFrameLayout lay{};
+    lay.nbytes = nbytes;
+    lay.dst_stride = dst_stride;
+    lay.blocksize = static_cast<uint32_t>(bs);
+    lay.nsplits = nsplits;
+    lay.rows_per = aqz::lz4_rows_per_chunk(nbytes, lay.blocksize, nsplits);
+    lay.flags = header_flags(p, bs);
+    lay.typesize = static_cast<uint8_t>(p.typesize);
+    lay.memcpy_only = memcpy_only;
+    if (!memcpy_only) {
+        const size_t total = nbytes * n_buffers;
+        if (const int rc = grow_device(&ctx->d_filtered, &ctx->d_cap, total); rc != AQZ_OK)
+            return rc;
+        if (const int rc = grow_device(&ctx->d_comp, &ctx->comp_cap, total + kHeader * n_buffers);
+            rc != AQZ_OK)
+            return rc;
+        if (const int rc = grow_device(&ctx->d_rows, &ctx->rows_cap,
+                                       size_t(lay.rows_per) * n_buffers * 2 * sizeof(uint32_t));
+            rc != AQZ_OK)
+            return rc;
+        BLOSC_HIP(aqz::launch_blosc_filter(p.shuffle, p.typesize, lay.blocksize, src, nbytes,
+                                           n_buffers, ctx->d_filtered, stream),
+                  "filter");
+        BLOSC_HIP(aqz::launch_lz4_splits(ctx->d_filtered, ctx->d_comp, ctx->d_rows, nbytes,
+                                         n_buffers, lay.blocksize, nsplits, 10 - p.clevel,
+                                         (flags & AQZ_LZ4_PROBE_SERIAL) != 0, stream),
+                  "lz4 splits");
+    }
+    BLOSC_HIP(aqz::launch_blosc_frames(src, ctx->d_filtered, ctx->d_comp, ctx->d_rows, d_dst,
+                                       d_sizes, n_buffers, lay, stream),
+              "frames");
+    return AQZ_OK;
+}
+
 } // namespace
 
 extern "C" {
+
+int
+aqz_debug_lz4_block_host(const void* src, size_t n, void* dst, size_t cap, int accel,
+                         uint32_t* need)
+{
+    try {
+        if ((!src && n) || (!dst && cap) || n > 0x7E000000u) {
+            aqz::set_last_error("debug_lz4_block_host: invalid argument");
+            return -1;
+        }
+        std::vector<uint32_t> table(aqz::lz4::kTableBytes / sizeof(uint32_t));
+        const uint32_t c = static_cast<uint32_t>(std::min<size_t>(cap, 0x7FFFFFFFu));
+        return static_cast<int>(aqz::lz4::encode_block(static_cast<const uint8_t*>(src),
+                                                       static_cast<uint32_t>(n),
+                                                       static_cast<uint8_t*>(dst), c, accel,
+                                                       table.data(), need));
+    } catch (...) {
+        (void)ABI_GUARD_FAIL(nullptr);
+        return -1;
+    }
+}
+
+int
+aqz_blosc_lz4_frames_device(aqz_blosc_ctx* ctx, int clevel, int shuffle, uint32_t typesize,
+                            const void* device_src, size_t nbytes, uint32_t n_buffers,
+                            void* device_dst, size_t dst_stride, uint32_t* device_frame_bytes,
+                            void* hip_stream, uint32_t flags)
+{
+    try {
+        Params p{};
+        if (const int rc = check_lz4_call(ctx, clevel, shuffle, typesize, device_src, nbytes,
+                                          n_buffers, device_dst, dst_stride, device_frame_bytes,
+                                          flags, &p);
+            rc != AQZ_OK)
+            return rc;
+        int prev = 0;
+        (void)hipGetDevice(&prev);
+        struct Restore
+        {
+            int d;
+            ~Restore() { (void)hipSetDevice(d); }
+        } restore{ prev };
+        BLOSC_HIP(hipSetDevice(ctx->device), "set device");
+        return queue_lz4_frames(ctx, p, static_cast<const uint8_t*>(device_src), nbytes, n_buffers,
+                                static_cast<uint8_t*>(device_dst), dst_stride, device_frame_bytes,
+                                static_cast<hipStream_t>(hip_stream), flags);
+    } catch (...) {
+        return ABI_GUARD_FAIL(nullptr);
+    }
+}
+
+int
+aqz_blosc_lz4_compress_device(aqz_blosc_ctx* ctx, int clevel, int shuffle, uint32_t typesize,
+                              const void* device_src, size_t nbytes, uint32_t n_buffers,
+                              void* host_dst, size_t dst_stride, size_t* frame_bytes,
+                              void* hip_stream, uint32_t flags)
+{
+    try {
+        Params p{};
+        if (const int rc = check_lz4_call(ctx, clevel, shuffle, typesize, device_src, nbytes,
+                                          n_buffers, host_dst, dst_stride, frame_bytes, flags, &p);
+            rc != AQZ_OK)
+            return rc;
+        int prev = 0;
+        (void)hipGetDevice(&prev);
+        struct Restore
+        {
+            int d;
+            ~Restore() { (void)hipSetDevice(d); }
+        } restore{ prev };
+        BLOSC_HIP(hipSetDevice(ctx->device), "set device");
+        auto stream = static_cast<hipStream_t>(hip_stream);
+        const size_t dev_stride = nbytes + kHeader;
+        const size_t sizes_bytes = sizeof(uint32_t) * n_buffers;
+        const size_t offs_at = (sizes_bytes + 7) / 8 * 8; // the uint64 offsets after the sizes
+        const size_t table_bytes = offs_at + sizeof(uint64_t) * n_buffers;
+        if (const int rc = grow_device(&ctx->d_frames, &ctx->frames_cap, dev_stride * n_buffers);
+            rc != AQZ_OK)
+            return rc;
+        if (const int rc = grow_device(&ctx->d_comp, &ctx->comp_cap, dev_stride * n_buffers);
+            rc != AQZ_OK)
+            return rc;
+        if (const int rc = grow_device(&ctx->d_table, &ctx->table_cap, table_bytes); rc != AQZ_OK)
+            return rc;
+        if (const int rc = grow_pinned(&ctx->h_table, &ctx->h_table_cap, table_bytes);
+            rc != AQZ_OK)
+            return rc;
+        auto* d_sizes = static_cast<uint32_t*>(ctx->d_table);
+        auto* d_offs = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(ctx->d_table) + offs_at);
+        auto* h_sizes = reinterpret_cast<uint32_t*>(ctx->h_table);
+        auto* h_offs = reinterpret_cast<uint64_t*>(ctx->h_table + offs_at);
+        // every exit drains `stream`: nothing of this call stays queued on
+        // the ctx's scratch
+        struct Drain
+        {
+            hipStream_t s;
+            ~Drain() { (void)hipStreamSynchronize(s); }
+        } drain{ stream };
+        if (const int rc = queue_lz4_frames(ctx, p, static_cast<const uint8_t*>(device_src),
+                                            nbytes, n_buffers,
+                                            static_cast<uint8_t*>(ctx->d_frames), dev_stride,
+                                            d_sizes, stream, flags);
+            rc != AQZ_OK)
+            return rc;
+        // the size table crosses first; then the frames, packed end to end on
+        // the device, in one copy
+        BLOSC_HIP(hipMemcpyAsync(h_sizes, d_sizes, sizes_bytes, hipMemcpyDeviceToHost, stream),
+                  "size table");
+        BLOSC_HIP(hipStreamSynchronize(stream), "sync");
+        uint64_t total = 0;
+        for (uint32_t k = 0; k < n_buffers; ++k) {
+            if (h_sizes[k] < kHeader || h_sizes[k] > dev_stride) {
+                aqz::set_last_error("blosc_lz4_compress_device: frame size out of range");
+                return AQZ_INTERNAL_ERROR;
+            }
+            h_offs[k] = total;
+            total += h_sizes[k];
+        }
+        if (const int rc = grow_pinned(&ctx->h_packed, &ctx->h_packed_cap, total); rc != AQZ_OK)
+            return rc;
+        BLOSC_HIP(hipMemcpyAsync(d_offs, h_offs, sizeof(uint64_t) * n_buffers,
+                                 hipMemcpyHostToDevice, stream),
+                  "offsets");
+        BLOSC_HIP(aqz::launch_pack_frames(ctx->d_frames, dev_stride, d_sizes, d_offs, ctx->d_comp,
+                                          n_buffers, stream),
+                  "pack");
+        BLOSC_HIP(hipMemcpyAsync(ctx->h_packed, ctx->d_comp, total, hipMemcpyDeviceToHost, stream),
+                  "frames");
+        BLOSC_HIP(hipStreamSynchronize(stream), "sync");
+        ctx->d2h_bytes = sizes_bytes + total;
+        auto* dst = static_cast<uint8_t*>(host_dst);
+        for (uint32_t k = 0; k < n_buffers; ++k) {
+            std::memcpy(dst + k * dst_stride, ctx->h_packed + h_offs[k], h_sizes[k]);
+            frame_bytes[k] = h_sizes[k];
+        }
+        return AQZ_OK;
+    } catch (...) {
+        return ABI_GUARD_FAIL(nullptr);
+    }
+}
+
+uint64_t
+aqz_debug_blosc_d2h_bytes(const aqz_blosc_ctx* ctx)
+{
+    return ctx ? ctx->d2h_bytes : 0;
+}
 
 int
 aqz_blosc_blocksize(int clevel, uint32_t typesize, size_t nbytes, const char* cname,

@@ -28,4 +28,60 @@ hipError_t launch_crc32c(const void* data,
                          uint32_t* crcs,
                          hipStream_t stream);
 
+// ---- blosc+LZ4 frames on the device (aqz_blosc_lz4_frames_device) ----------
+
+// Rows (csize, need) a chunk has: `nsplits` per full block, one for the
+// short leftover block.
+uint32_t lz4_rows_per_chunk(uint64_t nbytes, uint32_t blocksize, uint32_t nsplits);
+
+// LZ4_compress_fast(split, slot, len, len, accel) for every split of
+// `n_buffers` filtered chunks (lz4_block.hh states the encoder): one wave per
+// split, its slot the split's own bytes of `comp` (laid out like `filtered`),
+// its row (uint32 csize, uint32 need) in `rows`; csize 0 when need > len.
+// `serial_probe`: one table probe at a time instead of 64 (A/B form).
+hipError_t launch_lz4_splits(const void* filtered,
+                             void* comp,
+                             void* rows,
+                             uint64_t nbytes,
+                             uint32_t n_buffers,
+                             uint32_t blocksize,
+                             uint32_t nsplits,
+                             int accel,
+                             bool serial_probe,
+                             hipStream_t stream);
+
+struct BloscFrameLayout
+{
+    uint64_t nbytes;
+    uint64_t dst_stride; // >= nbytes + 16
+    uint32_t blocksize;  // compute_blocksize
+    uint32_t nsplits;    // splits of a full block: typesize or 1
+    uint32_t rows_per;   // lz4_rows_per_chunk
+    uint8_t flags;       // header_flags, without the memcpy bit
+    uint8_t typesize;
+    bool memcpy_only;    // clevel 0 or nbytes < 128: no rows are read
+};
+
+// The c-blosc frame of every chunk from its rows, slots and filtered bytes
+// (blocks_frame's walk), or the memcpy frame from `src` where c-blosc falls
+// back to it: frame k at dst + k * dst_stride, its size in sizes[k].
+hipError_t launch_blosc_frames(const void* src,
+                               const void* filtered,
+                               const void* comp,
+                               const void* rows,
+                               void* dst,
+                               uint32_t* sizes,
+                               uint32_t n_buffers,
+                               const BloscFrameLayout& layout,
+                               hipStream_t stream);
+
+// Frame k (sizes[k] bytes) from frames + k * stride to packed + offsets[k].
+hipError_t launch_pack_frames(const void* frames,
+                              uint64_t stride,
+                              const uint32_t* sizes,
+                              const uint64_t* offsets,
+                              void* packed,
+                              uint32_t n_buffers,
+                              hipStream_t stream);
+
 } // namespace aqz

@@ -17,6 +17,7 @@
 // compare against is oracle/codec_oracle.c.
 #include "codec_kernels.hh"
 #include "launch_log.hh"
+#include "lz4_block.hh"
 
 #include <hip/hip_runtime.h>
 
@@ -726,6 +727,550 @@ launch_crc32c(const void* data, uint64_t nbytes, uint64_t stride, uint32_t n_buf
                            dim3(kCrcThreadsPerWg), 0, stream, static_cast<const uint8_t*>(data),
                            nbytes, stride, uint32_t(wgs), n_buffers, 8u, pw, preset, crcs);
     }
+    return hipGetLastError();
+}
+
+// ---- lz4 splits and blosc frames --------------------------------------------
+//
+// The entropy stage of a blosc+LZ4 chunk on the device: one wave per split
+// runs the encoder lz4_block.hh states serially, and one workgroup per chunk
+// lays the frame out as blocks_frame / write_frame do on the host
+// (blosc_frame.cpp).  Every value that steers the encoder is wave-uniform
+// (ballots, lane reads, loads of one address), so all 64 lanes take the same
+// path; the lanes share the table clear, the probes of a search, the match
+// count and the copies.
+
+namespace {
+
+using lz4::kTableBytes;
+
+__device__ __forceinline__ uint32_t
+uni(uint32_t v)
+{
+    return __builtin_amdgcn_readfirstlane(v);
+}
+
+__device__ __forceinline__ uint32_t
+lane_read(uint32_t v, uint32_t lane)
+{
+    return __builtin_amdgcn_readlane(v, uni(lane));
+}
+
+__device__ __forceinline__ void
+store32(uint8_t* p, uint32_t v)
+{
+    __builtin_memcpy(p, &v, 4);
+}
+
+// dst[0, len) = src[0, len), any alignment, by the whole wave
+__device__ __forceinline__ void
+wave_copy(uint8_t* dst, const uint8_t* src, uint32_t len, uint32_t lane)
+{
+    const uint32_t words = len >> 2;
+    for (uint32_t i = lane; i < words; i += 64)
+        store32(dst + 4 * i, lz4::read32(src + 4 * i));
+    for (uint32_t i = (words << 2) + lane; i < len; i += 64)
+        dst[i] = src[i];
+}
+
+// the bytes after a token nibble of 15 (lz4::put_length), by the whole wave
+__device__ __forceinline__ uint32_t
+wave_put_length(uint8_t* dst, uint32_t len, uint32_t lane)
+{
+    const uint32_t m = len - 15, q = m / 255;
+    for (uint32_t i = lane; i < q; i += 64)
+        dst[i] = 255;
+    if (lane == 0)
+        dst[q] = uint8_t(m - q * 255);
+    return q + 1;
+}
+
+// equal bytes of src[a...] and src[b...] (b < a) before `limit`: four bytes a
+// lane, 256 a step, the first lane that stops found by ballot
+__device__ __forceinline__ uint32_t
+wave_count(const uint8_t* src, uint32_t a, uint32_t b, uint32_t limit, uint32_t lane)
+{
+    uint32_t total = 0;
+    for (;;) {
+        const uint32_t pos = a + total + 4 * lane;
+        const uint32_t ref = b + total + 4 * lane;
+        uint32_t c = 0;
+        if (pos + 4 <= limit) {
+            const uint32_t x = lz4::read32(src + pos) ^ lz4::read32(src + ref);
+            c = x ? uint32_t(__builtin_ctz(x)) >> 3 : 4u;
+        } else {
+            while (c < 3 && pos + c < limit && src[pos + c] == src[ref + c])
+                ++c;
+        }
+        const uint64_t stop = __ballot(c < 4);
+        if (stop) {
+            const uint32_t l = uint32_t(__ffsll(static_cast<long long>(stop))) - 1;
+            return total + 4 * l + lane_read(c, l);
+        }
+        total += 256; // every lane had four bytes before limit: pos advances
+    }
+}
+
+// sum over t < x of t >> 6: the bytes the step schedule skips
+__device__ __forceinline__ uint64_t
+skip_sum(uint32_t x)
+{
+    const uint64_t q = x >> 6, r = x & 63;
+    return 32 * q * (q - 1) + q * r;
+}
+
+enum SearchEnd
+{
+    kSearchInputEnd = 0, // the next probe would pass end - 11: last literals
+    kSearchFound = 1,
+    kSearchMore = 2 // `max_probes` probes made, none matched
+};
+
+// One search, one probe at a time (the A/B form, and the first probes of the
+// batched form): lane 0 owns the table.
+template<typename T>
+__device__ __forceinline__ SearchEnd
+search_serial(const uint8_t* src, T* table, uint32_t ip, uint32_t mflimit1, uint32_t accel,
+              uint32_t lane, uint32_t max_probes, uint32_t* p_out, uint32_t* cand_out)
+{
+    uint32_t next = ip, step = 1, nb = accel << lz4::kSkipTrigger;
+    for (uint32_t g = 0; g < max_probes; ++g) {
+        const uint32_t p = next;
+        next += step; // step >= 1: accel >= 1
+        step = nb++ >> lz4::kSkipTrigger;
+        if (next > mflimit1)
+            return kSearchInputEnd;
+        const lz4::Table<T> tab{ table };
+        const uint32_t h = uni(tab.hash(src + p));
+        const uint32_t v = uni(lz4::read32(src + p));
+        uint32_t c = 0;
+        if (lane == 0) {
+            c = table[h];
+            table[h] = T(p);
+        }
+        const uint32_t cand = uni(c);
+        if (lz4::Table<T>::near(cand, p) && uni(lz4::read32(src + cand)) == v) {
+            *p_out = p;
+            *cand_out = cand;
+            return kSearchFound;
+        }
+    }
+    return kSearchMore;
+}
+
+// Probes a batched search makes one at a time before it goes 64 wide: in
+// compressible data most searches end within their first few probes, and a
+// batch costs a 64-step conflict scan on top of the two loads.  A search that
+// has missed this often is likely a long one (incompressible data, where the
+// steps grow), which is what the batches are for.
+constexpr uint32_t kSerialLead = 8;
+
+// One search, 64 probes at a time.  The probe positions do not depend on the
+// data, so lane i takes probe g0 + i.  A lane whose bucket an earlier lane of
+// the batch also probes gets that lane's position as its candidate (the
+// nearest one), which is what the serial order of lookups and stores yields;
+// the first lane whose candidate passes is the match, and only the lanes up to
+// it store, the latest of a bucket winning.
+template<typename T>
+__device__ __forceinline__ bool
+search_batch(const uint8_t* src, T* table, uint32_t ip, uint32_t mflimit1, uint32_t accel,
+             uint32_t lane, uint32_t* p_out, uint32_t* cand_out)
+{
+    const uint32_t nb0 = accel << lz4::kSkipTrigger;
+    const uint64_t f0 = skip_sum(nb0);
+    const lz4::Table<T> tab{ table };
+    const SearchEnd lead =
+      search_serial<T>(src, table, ip, mflimit1, accel, lane, kSerialLead, p_out, cand_out);
+    if (lead != kSearchMore)
+        return lead == kSearchFound;
+    for (uint32_t g0 = kSerialLead;; g0 += 64) {
+        __syncthreads(); // earlier stores, by any lane, before these lookups
+        const uint32_t g = g0 + lane;
+        const uint64_t at = ip + (g ? 1 + skip_sum(nb0 + g - 1) - f0 : 0);
+        const uint64_t nxt_at = ip + 1 + skip_sum(nb0 + g) - f0;
+        const bool valid = nxt_at <= mflimit1; // a prefix of the lanes
+        const uint32_t p = valid ? uint32_t(at) : 0;
+        uint32_t h = 0xFFFFFFFFu, v = 0, c = 0;
+        if (valid) {
+            h = tab.hash(src + p);
+            v = lz4::read32(src + p);
+            c = table[h];
+        }
+        int prev = -1, nxt = 64;
+#pragma unroll
+        for (int j = 0; j < 64; ++j) {
+            const uint32_t hj = __builtin_amdgcn_readlane(h, j);
+            if (hj == h) {
+                if (j < int(lane))
+                    prev = j;
+                else if (j > int(lane) && nxt == 64)
+                    nxt = j;
+            }
+        }
+        const uint32_t pc = __shfl(p, prev < 0 ? 0 : prev);
+        const uint32_t pv = __shfl(v, prev < 0 ? 0 : prev);
+        uint32_t cv = pv;
+        if (prev >= 0)
+            c = pc;
+        else if (valid)
+            cv = lz4::read32(src + c);
+        const bool hit = valid && lz4::Table<T>::near(c, p) && cv == v;
+        const uint64_t hits = __ballot(hit);
+        const uint64_t invalid = __ballot(!valid);
+        const uint32_t m = hits ? uint32_t(__ffsll(static_cast<long long>(hits))) - 1 : 63u;
+        if (valid && lane <= m && nxt > int(m))
+            table[h] = T(p);
+        if (hits) {
+            __syncthreads();
+            *p_out = lane_read(p, m);
+            *cand_out = lane_read(c, m);
+            return true;
+        }
+        if (invalid)
+            return false;
+        // 64 valid probes: the next batch starts at least 64 bytes further on
+    }
+}
+
+struct Lz4Run
+{
+    uint64_t stride;   // bytes between chunks
+    uint64_t first;    // offset of the run's first split within a chunk
+    uint32_t per;      // splits of the run per chunk
+    uint32_t len;      // bytes per split
+    uint32_t row0;     // the run's first row among a chunk's rows
+    uint32_t rows_per; // rows per chunk
+    uint32_t accel;
+};
+
+// One wave per split: slot = the split's own bytes in `comp`, row = (csize,
+// need), csize 0 when need passed the split size.
+template<typename T, bool BATCH>
+__global__ __launch_bounds__(64) void
+lz4_split_kernel(const uint8_t* __restrict__ filt, uint8_t* __restrict__ comp,
+                 uint2* __restrict__ rows, Lz4Run run)
+{
+    __shared__ T table[kTableBytes / sizeof(T)];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t k = blockIdx.x / run.per, j = blockIdx.x % run.per;
+    const uint64_t base = uint64_t(k) * run.stride + run.first + uint64_t(j) * run.len;
+    const uint8_t* src = filt + base;
+    uint8_t* dst = comp + base;
+    const uint32_t n = run.len, cap = run.len;
+    {
+        auto* w = reinterpret_cast<uint32_t*>(table);
+        for (uint32_t i = lane; i < kTableBytes / 4; i += 64)
+            w[i] = 0;
+    }
+    __syncthreads();
+    const lz4::Table<T> tab{ table };
+    uint64_t need = 0;
+    uint32_t op = 0, anchor = 0;
+    bool fits = true;
+    auto over = [&](uint64_t x) {
+        need = x > need ? x : need;
+        return x > cap;
+    };
+    if (n >= lz4::kMinInput) {
+        const uint32_t mflimit1 = n - lz4::kMfLimit;
+        const uint32_t matchlimit = n - lz4::kLastLiterals;
+        // position 0 goes into the table: the cleared entry already says so
+        uint32_t ip = 1;
+        for (;;) {
+            uint32_t p = 0, cand = 0;
+            const bool found =
+              BATCH ? search_batch<T>(src, table, ip, mflimit1, run.accel, lane, &p, &cand)
+                    : search_serial<T>(src, table, ip, mflimit1, run.accel, lane, 0xFFFFFFFFu, &p,
+                                       &cand) == kSearchFound;
+            if (!found)
+                break;
+            // backwards to the anchor, 64 bytes a step
+            for (uint32_t back = 0;;) {
+                const uint32_t room = (p - anchor < cand ? p - anchor : cand) - back;
+                if (room == 0) {
+                    p -= back;
+                    cand -= back;
+                    break;
+                }
+                bool eq = false;
+                if (lane < room)
+                    eq = src[p - 1 - back - lane] == src[cand - 1 - back - lane];
+                const uint64_t stop = __ballot(!eq);
+                const uint32_t c = stop ? uint32_t(__ffsll(static_cast<long long>(stop))) - 1 : 64u;
+                back += c; // c <= room
+                if (c < 64) {
+                    p -= back;
+                    cand -= back;
+                    break;
+                }
+            }
+            const uint32_t lit = p - anchor;
+            if (over(op + lz4::bound_literals(lit))) {
+                fits = false;
+                break;
+            }
+            uint32_t token_at = op++;
+            uint32_t token = lit >= 15 ? 0xF0u : lit << 4;
+            if (lit >= 15)
+                op += wave_put_length(dst + op, lit, lane);
+            wave_copy(dst + op, src + anchor, lit, lane);
+            op += lit;
+            for (;;) {
+                const uint32_t off = p - cand;
+                if (lane == 0) {
+                    dst[op] = uint8_t(off);
+                    dst[op + 1] = uint8_t(off >> 8);
+                }
+                op += 2;
+                const uint32_t count = wave_count(src, p + 4, cand + 4, matchlimit, lane);
+                if (over(op + lz4::bound_match(count))) {
+                    fits = false;
+                    break;
+                }
+                if (count >= 15) {
+                    token |= 15;
+                    op += wave_put_length(dst + op, count, lane);
+                } else {
+                    token |= count;
+                }
+                if (lane == 0)
+                    dst[token_at] = uint8_t(token);
+                anchor = ip = p + 4 + count;
+                if (ip >= mflimit1)
+                    break;
+                // store ip - 2, then look ip up and store it
+                const uint32_t h2 = uni(tab.hash(src + ip - 2));
+                const uint32_t h = uni(tab.hash(src + ip));
+                const uint32_t v = uni(lz4::read32(src + ip));
+                uint32_t c = 0;
+                if (lane == 0) {
+                    table[h2] = T(ip - 2);
+                    c = table[h];
+                    table[h] = T(ip);
+                }
+                cand = uni(c);
+                if (!(lz4::Table<T>::near(cand, ip) && uni(lz4::read32(src + cand)) == v))
+                    break;
+                p = ip;
+                token_at = op++;
+                token = 0;
+            }
+            if (!fits || ip >= mflimit1)
+                break;
+            ++ip;
+        }
+    }
+    if (fits) {
+        const uint32_t last = n - anchor;
+        if (over(op + lz4::bound_last(last))) {
+            fits = false;
+        } else {
+            if (lane == 0)
+                dst[op] = uint8_t(last >= 15 ? 0xF0u : last << 4);
+            ++op;
+            if (last >= 15)
+                op += wave_put_length(dst + op, last, lane);
+            wave_copy(dst + op, src + anchor, last, lane);
+            op += last;
+        }
+    }
+    if (lane == 0)
+        rows[uint64_t(k) * run.rows_per + run.row0 + j] =
+          make_uint2(fits ? op : 0u, need > 0xFFFFFFFFull ? 0xFFFFFFFFu : uint32_t(need));
+}
+
+// dst[0, len) = src[0, len), any alignment, by a 256-thread workgroup
+__device__ __forceinline__ void
+wg_copy(uint8_t* dst, const uint8_t* src, uint64_t len, uint32_t t)
+{
+    const uint64_t vecs = len >> 4;
+    for (uint64_t i = t; i < vecs; i += 256)
+        *reinterpret_cast<u32x4_u*>(dst + 16 * i) = *reinterpret_cast<const u32x4_u*>(src + 16 * i);
+    for (uint64_t i = (vecs << 4) + t; i < len; i += 256)
+        dst[i] = src[i];
+}
+
+__device__ __forceinline__ void
+put32_dev(uint8_t* d, uint32_t v)
+{
+    d[0] = uint8_t(v);
+    d[1] = uint8_t(v >> 8);
+    d[2] = uint8_t(v >> 16);
+    d[3] = uint8_t(v >> 24);
+}
+
+// One workgroup per chunk.  Every thread walks the chunk's rows the way
+// blocks_frame does (blosc_frame.cpp), once to learn whether c-blosc would
+// fall back to the memcpy frame and once to place the splits; the workgroup
+// copies each payload.  `memcpy_only`: clevel 0 or nbytes < 128.
+__global__ __launch_bounds__(256) void
+blosc_frame_kernel(const uint8_t* __restrict__ src, const uint8_t* __restrict__ filt,
+                   const uint8_t* __restrict__ comp, const uint2* __restrict__ rows,
+                   uint8_t* __restrict__ dst, uint32_t* __restrict__ sizes, BloscFrameLayout lay)
+{
+    const uint32_t k = blockIdx.x, t = threadIdx.x;
+    uint8_t* out = dst + uint64_t(k) * lay.dst_stride;
+    const uint64_t chunk = uint64_t(k) * lay.nbytes;
+    const uint2* row = rows + uint64_t(k) * lay.rows_per;
+    const uint64_t destsize = lay.nbytes + 16;
+    const uint32_t nblocks = uint32_t((lay.nbytes + lay.blocksize - 1) / lay.blocksize);
+    // pass 0 decides, pass 1 writes
+    bool fallback = lay.memcpy_only;
+    uint64_t total = 0;
+    for (int pass = 0; pass < 2 && !fallback; ++pass) {
+        uint64_t nt = 16 + 4 * uint64_t(nblocks);
+        if (nt > destsize) {
+            fallback = true;
+            break;
+        }
+        uint32_t r = 0;
+        for (uint32_t b = 0; b < nblocks && !fallback; ++b) {
+            const uint64_t off = uint64_t(b) * lay.blocksize;
+            const uint64_t bsize = lay.nbytes - off < lay.blocksize ? lay.nbytes - off : lay.blocksize;
+            const uint32_t nsplits = bsize < lay.blocksize ? 1u : lay.nsplits;
+            const uint64_t neb = bsize / nsplits;
+            if (pass && t == 0)
+                put32_dev(out + 16 + 4 * b, uint32_t(nt));
+            for (uint32_t j = 0; j < nsplits; ++j, ++r) {
+                nt += 4;
+                if (nt >= destsize) {
+                    fallback = true;
+                    break;
+                }
+                const uint64_t cap = neb < destsize - nt ? neb : destsize - nt;
+                const uint2 cn = row[r];
+                const bool packed = cn.x != 0 && cn.y <= cap && cn.x != neb;
+                if (!packed && nt + neb > destsize) {
+                    fallback = true;
+                    break;
+                }
+                const uint64_t c = packed ? cn.x : neb;
+                if (pass) {
+                    if (t == 0)
+                        put32_dev(out + nt - 4, uint32_t(c));
+                    const uint64_t piece = chunk + off + uint64_t(j) * neb;
+                    wg_copy(out + nt, (packed ? comp : filt) + piece, c, t);
+                }
+                nt += c;
+            }
+        }
+        total = nt;
+    }
+    uint8_t flags = lay.flags;
+    if (fallback) {
+        flags |= 0x2;
+        total = destsize;
+        wg_copy(out + 16, src + chunk, lay.nbytes, t);
+    }
+    if (t == 0) {
+        out[0] = 2; // BLOSC_VERSION_FORMAT
+        out[1] = 1; // versionlz of lz4
+        out[2] = flags;
+        out[3] = lay.typesize;
+        put32_dev(out + 4, uint32_t(lay.nbytes));
+        put32_dev(out + 8, lay.blocksize);
+        put32_dev(out + 12, uint32_t(total));
+        sizes[k] = uint32_t(total);
+    }
+}
+
+// frame k (sizes[k] bytes at frames + k * stride) to packed + offsets[k]
+__global__ __launch_bounds__(256) void
+pack_frames_kernel(const uint8_t* __restrict__ frames, uint64_t stride,
+                   const uint32_t* __restrict__ sizes, const uint64_t* __restrict__ offsets,
+                   uint8_t* __restrict__ packed)
+{
+    const uint32_t k = blockIdx.x;
+    wg_copy(packed + offsets[k], frames + uint64_t(k) * stride, sizes[k], threadIdx.x);
+}
+
+template<typename T>
+void
+launch_split_run(const uint8_t* filt, uint8_t* comp, uint2* rows, const Lz4Run& run, uint32_t grid,
+                 bool serial, hipStream_t stream)
+{
+    if (launch_log_on())
+        launch_log_record("family=lz4 table=%s probe=%s streams=%u grid=%u block=64 len=%u "
+                          "accel=%u",
+                          sizeof(T) == 2 ? "u16" : "u32", serial ? "serial" : "batch", grid, grid,
+                          run.len, run.accel);
+    if (serial)
+        hipLaunchKernelGGL((lz4_split_kernel<T, false>), dim3(grid), dim3(64), 0, stream, filt,
+                           comp, rows, run);
+    else
+        hipLaunchKernelGGL((lz4_split_kernel<T, true>), dim3(grid), dim3(64), 0, stream, filt, comp,
+                           rows, run);
+}
+
+} // namespace
+
+uint32_t
+lz4_rows_per_chunk(uint64_t nbytes, uint32_t blocksize, uint32_t nsplits)
+{
+    return uint32_t(nbytes / blocksize) * nsplits + (nbytes % blocksize ? 1u : 0u);
+}
+
+hipError_t
+launch_lz4_splits(const void* filtered, void* comp, void* rows, uint64_t nbytes,
+                  uint32_t n_buffers, uint32_t blocksize, uint32_t nsplits, int accel,
+                  bool serial_probe, hipStream_t stream)
+{
+    if (blocksize == 0 || nsplits == 0 || n_buffers == 0 || nbytes == 0 || blocksize % nsplits)
+        return hipErrorInvalidValue;
+    const uint64_t full = nbytes / blocksize;
+    const uint32_t leftover = uint32_t(nbytes % blocksize);
+    const uint64_t rows_per = full * nsplits + (leftover ? 1 : 0);
+    if (rows_per * n_buffers >= (1ull << 31))
+        return hipErrorInvalidValue;
+    const auto* f = static_cast<const uint8_t*>(filtered);
+    auto* c = static_cast<uint8_t*>(comp);
+    auto* r = static_cast<uint2*>(rows);
+    const uint32_t acc = uint32_t(lz4::clamp_accel(accel));
+    auto go = [&](const Lz4Run& run) {
+        const uint32_t grid = run.per * n_buffers;
+        if (run.len < lz4::kU16Limit)
+            launch_split_run<uint16_t>(f, c, r, run, grid, serial_probe, stream);
+        else
+            launch_split_run<uint32_t>(f, c, r, run, grid, serial_probe, stream);
+        return hipGetLastError();
+    };
+    if (full) {
+        const Lz4Run run{ nbytes, 0, uint32_t(full * nsplits), blocksize / nsplits, 0,
+                          uint32_t(rows_per), acc };
+        if (const hipError_t e = go(run); e != hipSuccess)
+            return e;
+    }
+    if (leftover) {
+        const Lz4Run run{ nbytes, full * blocksize, 1, leftover, uint32_t(full * nsplits),
+                          uint32_t(rows_per), acc };
+        return go(run);
+    }
+    return hipSuccess;
+}
+
+hipError_t
+launch_blosc_frames(const void* src, const void* filtered, const void* comp, const void* rows,
+                    void* dst, uint32_t* sizes, uint32_t n_buffers, const BloscFrameLayout& layout,
+                    hipStream_t stream)
+{
+    if (n_buffers == 0 || n_buffers >= (1u << 31) || layout.blocksize == 0 || layout.nsplits == 0)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(blosc_frame_kernel, dim3(n_buffers), dim3(256), 0, stream,
+                       static_cast<const uint8_t*>(src), static_cast<const uint8_t*>(filtered),
+                       static_cast<const uint8_t*>(comp), static_cast<const uint2*>(rows),
+                       static_cast<uint8_t*>(dst), sizes, layout);
+    return hipGetLastError();
+}
+
+hipError_t
+launch_pack_frames(const void* frames, uint64_t stride, const uint32_t* sizes,
+                   const uint64_t* offsets, void* packed, uint32_t n_buffers, hipStream_t stream)
+{
+    if (n_buffers == 0 || n_buffers >= (1u << 31))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pack_frames_kernel, dim3(n_buffers), dim3(256), 0, stream,
+                       static_cast<const uint8_t*>(frames), stride, sizes, offsets,
+                       static_cast<uint8_t*>(packed));
     return hipGetLastError();
 }
 

@@ -106,6 +106,71 @@ int aqz_blosc_compress_device(aqz_blosc_ctx* ctx,
                               size_t* frame_bytes,
                               void* hip_stream);
 
+/*
+ * The same lz4 frames with the entropy coder on the device as well: after the
+ * filter, one wave per blosc split runs LZ4's fast block encoder
+ * (LZ4_compress_fast on a fresh state, acceleration 10 - clevel, restated in
+ * csrc/lz4_block.hh) into a slot of the split's own size, and one workgroup
+ * per chunk lays out the frame c-blosc would write, raw splits and the
+ * whole-chunk memcpy fallback included.  Only "lz4"; zstd stays on the host
+ * (aqz_blosc_compress_device).  The frames are byte-identical to that call's.
+ *
+ * flags: AQZ_LZ4_PROBE_SERIAL makes a search probe the hash table one
+ * position at a time; by default (0) the 64 lanes of a wave take the next 64
+ * probe positions at once.  Both give the same bytes; any other bit is
+ * AQZ_INVALID_ARGUMENT.
+ */
+#define AQZ_LZ4_PROBE_SERIAL 1u
+
+/* filter + LZ4 + frame, all on hip_stream, no synchronisation: frame k at
+ * device_dst + k * dst_stride (dst_stride >= nbytes + 16), its size in
+ * device_frame_bytes[k]. lz4 only. Scratch grows inside ctx. */
+int aqz_blosc_lz4_frames_device(aqz_blosc_ctx* ctx,
+                                int clevel,
+                                int shuffle,
+                                uint32_t typesize,
+                                const void* device_src,
+                                size_t nbytes,
+                                uint32_t n_buffers,
+                                void* device_dst,
+                                size_t dst_stride,
+                                uint32_t* device_frame_bytes,
+                                void* hip_stream,
+                                uint32_t flags);
+
+/* same frames delivered like aqz_blosc_compress_device (host_dst, dst_stride,
+ * frame_bytes), but only frame bytes and the size table cross PCIe: the
+ * frames are packed end to end on the device and copied once.  Returns when
+ * every frame is written. */
+int aqz_blosc_lz4_compress_device(aqz_blosc_ctx* ctx,
+                                  int clevel,
+                                  int shuffle,
+                                  uint32_t typesize,
+                                  const void* device_src,
+                                  size_t nbytes,
+                                  uint32_t n_buffers,
+                                  void* host_dst,
+                                  size_t dst_stride,
+                                  size_t* frame_bytes,
+                                  void* hip_stream,
+                                  uint32_t flags);
+
+/* Test seams.  Bytes the last aqz_blosc_lz4_compress_device on `ctx` copied
+ * from device to host (size table + packed frames). */
+uint64_t aqz_debug_blosc_d2h_bytes(const aqz_blosc_ctx* ctx);
+
+/* The serial encoder of csrc/lz4_block.hh on host memory, no GPU involved:
+ * LZ4_compress_fast(src, dst, n, cap, accel) on a fresh state.  Returns the
+ * compressed size, 0 when it does not fit into cap, -1 for a bad argument.
+ * *need (may be NULL): the capacity the bytes written asked for; the result
+ * is non-zero exactly when *need <= cap. */
+int aqz_debug_lz4_block_host(const void* src,
+                             size_t n,
+                             void* dst,
+                             size_t cap,
+                             int accel,
+                             uint32_t* need);
+
 /* Which LZ4 and zstd libraries the frame writer loaded, with versions
  * ("" entries for a codec that failed to load).  $AQZ_LZ4_LIB and
  * $AQZ_ZSTD_LIB name them explicitly. */
