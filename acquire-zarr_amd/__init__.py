@@ -46,7 +46,7 @@ EXPORTS = (
     "aqz_blosc_blocksize", "aqz_blosc_frame_from_filtered", "aqz_blosc_ctx_create",
     "aqz_blosc_ctx_destroy", "aqz_blosc_compress_device", "aqz_blosc_codec_info",
     "aqz_blosc_lz4_frames_device", "aqz_blosc_lz4_compress_device",
-    "aqz_debug_blosc_d2h_bytes", "aqz_debug_lz4_block_host",
+    "aqz_debug_blosc_d2h_bytes", "aqz_debug_lz4_block_host", "aqz_debug_lz4_splits_device",
     "aqz_ds_level_bytes", "aqz_ds_level_count", "aqz_ds_device_memory_usage",
     "aqz_ds_device",
     "aqz_ds_last_error", "aqz_last_error", "aqz_method_name",
@@ -165,6 +165,7 @@ def lib() -> ctypes.CDLL:
     L.aqz_debug_blosc_d2h_bytes.argtypes = [vp]
     L.aqz_debug_blosc_d2h_bytes.restype = ctypes.c_uint64
     L.aqz_debug_lz4_block_host.argtypes = [vp, sz, vp, sz, ctypes.c_int, ctypes.POINTER(u32)]
+    L.aqz_debug_lz4_splits_device.argtypes = [vp, vp, sz, u32, ctypes.c_int, vp, vp, vp, u32]
     L.aqz_blosc_codec_info.argtypes = []
     L.aqz_blosc_codec_info.restype = ctypes.c_char_p
     L.aqz_ds_add_device_frame.argtypes = [vp, vp, sz]
@@ -769,6 +770,16 @@ class BloscContext:
     def d2h_bytes(self) -> int:
         """Bytes the last lz4_compress_device copied from device to host."""
         return lib().aqz_debug_blosc_d2h_bytes(self._h)
+
+    def debug_lz4_splits_device(self, device_src: int, split_bytes: int, n_splits: int,
+                                accel: int, device_comp: int, device_rows: int, stream: int = 0,
+                                flags: int = 0):
+        """aqz_debug_lz4_splits_device: the device encoder on raw splits,
+        asynchronous on `stream`; split k into its own range of `device_comp`,
+        its (csize, need) at the device uint32 array `device_rows`[2k]."""
+        _raise_if(lib().aqz_debug_lz4_splits_device(
+            self._h, device_src, split_bytes, n_splits, accel, device_comp, device_rows,
+            ctypes.c_void_p(stream) if stream else None, flags))
 
 
 LZ4_PROBE_SERIAL = 1  # aqz_blosc.h

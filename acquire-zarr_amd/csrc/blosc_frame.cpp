@@ -526,6 +526,38 @@ aqz_debug_lz4_block_host(const void* src, size_t n, void* dst, size_t cap, int a
 }
 
 int
+aqz_debug_lz4_splits_device(aqz_blosc_ctx* ctx, const void* device_src, size_t split_bytes,
+                            uint32_t n_splits, int accel, void* device_comp,
+                            uint32_t* device_rows, void* hip_stream, uint32_t flags)
+{
+    try {
+        if (!ctx || !device_src || !device_comp || !device_rows || n_splits == 0 ||
+            split_bytes == 0 || split_bytes > 0x7E000000u ||
+            (flags & ~uint32_t(AQZ_LZ4_PROBE_SERIAL)) != 0) {
+            aqz::set_last_error("debug_lz4_splits_device: invalid argument");
+            return AQZ_INVALID_ARGUMENT;
+        }
+        int prev = 0;
+        (void)hipGetDevice(&prev);
+        struct Restore
+        {
+            int d;
+            ~Restore() { (void)hipSetDevice(d); }
+        } restore{ prev };
+        BLOSC_HIP(hipSetDevice(ctx->device), "set device");
+        // every split a chunk of one block of one split: slot and row k
+        BLOSC_HIP(aqz::launch_lz4_splits(device_src, device_comp, device_rows, split_bytes,
+                                         n_splits, static_cast<uint32_t>(split_bytes), 1, accel,
+                                         (flags & AQZ_LZ4_PROBE_SERIAL) != 0,
+                                         static_cast<hipStream_t>(hip_stream)),
+                  "lz4 splits");
+        return AQZ_OK;
+    } catch (...) {
+        return ABI_GUARD_FAIL(nullptr);
+    }
+}
+
+int
 aqz_blosc_lz4_frames_device(aqz_blosc_ctx* ctx, int clevel, int shuffle, uint32_t typesize,
                             const void* device_src, size_t nbytes, uint32_t n_buffers,
                             void* device_dst, size_t dst_stride, uint32_t* device_frame_bytes,

@@ -171,6 +171,24 @@ int aqz_debug_lz4_block_host(const void* src,
                              int accel,
                              uint32_t* need);
 
+/* The device encoder on raw splits, without filter or frame: `n_splits`
+ * splits of `split_bytes` each, back to back at `device_src`, one wave per
+ * split on `hip_stream`, no synchronisation.  Split k is encoded into its own
+ * range [k * split_bytes, (k + 1) * split_bytes) of `device_comp` (capacity
+ * split_bytes, as in a frame) and its row (csize, need) goes to
+ * device_rows[2k], device_rows[2k + 1]: csize 0 when need passed split_bytes.
+ * `ctx` names the device only; none of its scratch is used.  flags as for
+ * aqz_blosc_lz4_frames_device. */
+int aqz_debug_lz4_splits_device(aqz_blosc_ctx* ctx,
+                                const void* device_src,
+                                size_t split_bytes,
+                                uint32_t n_splits,
+                                int accel,
+                                void* device_comp,
+                                uint32_t* device_rows,
+                                void* hip_stream,
+                                uint32_t flags);
+
 /* Which LZ4 and zstd libraries the frame writer loaded, with versions
  * ("" entries for a codec that failed to load).  $AQZ_LZ4_LIB and
  * $AQZ_ZSTD_LIB name them explicitly. */

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import blosc_ref
+import lz4_cases
 from gpu_util import empty_device, from_device, launch_stream, to_device, torch_cuda
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -256,6 +257,65 @@ def test_host_delivery_and_pcie_bytes(aqz, ctx, flags):
     for k in range(n):
         assert host[k * stride:k * stride + sizes[k]].tobytes() == want[k]
         assert (host[k * stride + sizes[k]:(k + 1) * stride] == POISON).all()
+
+
+@pytest.mark.parametrize("flags", FLAGS)
+def test_single_split_chunk_at_its_capacity(aqz, ctx, flags):
+    """A chunk of one split (typesize 1) has nbytes - 8 bytes for it: 16 of
+    header, 4 of block start and 4 of split size out of nbytes + 16.  need ==
+    nbytes - 8 is the last packed frame, need == nbytes - 7 the first memcpy
+    one; the split's row alone decides."""
+    n = 32768
+    found = lz4_cases.capacity_scan(aqz, n, 1, 81, wanted=(-8, -7))
+    assert sorted(found) == [-8, -7]
+    for d in (-8, -7):
+        assert aqz.debug_lz4_block_host(found[d], n, 1)[2] == n + d
+    raw = np.concatenate([found[-8], found[-7]])
+    want = check_case(aqz, ctx, ("onesplit",), raw, n, 2, 9, 0, 1, flags)
+    packed, memcpyed = want
+    assert blosc_ref.header(packed)["blocksize"] == n and not packed[2] & 0x12
+    (((csize, _),),) = blosc_ref.stored_splits(packed)
+    assert csize == aqz.debug_lz4_block_host(found[-8], n, 1)[0] and len(packed) == 24 + csize
+    assert memcpyed[2] & 0x2 and len(memcpyed) == n + 16
+    assert memcpyed[16:] == found[-7].tobytes()
+
+
+@pytest.mark.parametrize("flags", FLAGS)
+def test_split_compressed_to_its_own_size_is_stored_raw(aqz, ctx, flags):
+    """csize == split size: c-blosc stores the filtered split, not the
+    encoder's output of the same length."""
+    n = 32768
+    split1 = lz4_cases.capacity_scan(aqz, n, 1, 82, wanted=(0,))[0]
+    csize, block, need = aqz.debug_lz4_block_host(split1, n, 1)
+    assert csize == need == n and block != split1.tobytes()
+    raw = np.zeros(2 * n, np.uint8)
+    raw[1::2] = split1  # byte 1 of every element: split 1 once shuffled
+    (frame,) = check_case(aqz, ctx, ("rawsplit",), raw, 2 * n, 1, 9, 1, 2, flags)
+    assert blosc_ref.header(frame)["blocksize"] == 2 * n and not frame[2] & 0x12
+    ((first, _), (second, payload)), = blosc_ref.stored_splits(frame)
+    assert first < 200 and second == n
+    assert payload == split1.tobytes()
+
+
+@pytest.mark.parametrize("flags", FLAGS)
+@pytest.mark.parametrize("r", [1, 3, 12, 13, 17])
+def test_short_leftover_blocks(aqz, ctx, r, flags):
+    """A leftover block of r bytes behind two full ones: one split below or at
+    the encoder's 13-byte minimum, not a multiple of the typesize."""
+    bs = aqz.blosc_blocksize(1, 4, 1 << 20, "lz4")
+    nbytes = 2 * bs + r
+    assert aqz.blosc_blocksize(1, 4, nbytes, "lz4") == bs
+    rng = np.random.default_rng(90 + r)
+    raw = np.empty(3 * nbytes, np.uint8)
+    for k in range(3):
+        body = smooth_chunks(rng, 1, 2 * bs // 1024, 256, np.float32)
+        raw[k * nbytes:k * nbytes + 2 * bs] = body.view(np.uint8).reshape(-1)
+        raw[k * nbytes + 2 * bs:(k + 1) * nbytes] = [7 * k] * r if k else rng.integers(0, 256, r)
+    want = check_case(aqz, ctx, ("leftover", r), raw, nbytes, 3, 1, 1, 4, flags)
+    for f in want:
+        assert not f[2] & 0x2
+        blocks = blosc_ref.stored_splits(f)
+        assert [len(b) for b in blocks] == [4, 4, 1]
 
 
 def test_errors(aqz, ctx):
