@@ -4,6 +4,7 @@
     python tests/golden/make_reference_vectors.py        # vectors + manifest
     python tests/golden/make_reference_vectors.py --digests   # + BASELINE digests
     python tests/golden/make_reference_vectors.py --nan-only  # NaN-payload set only
+    python tests/golden/make_reference_vectors.py --float-classes  # float-class set only
 
 Every output byte here comes from acquire-zarr v0.8.1's own
 zarr::Downsampler / ArrayDimensions (src/streaming/downsampler.cpp,
@@ -118,6 +119,39 @@ def nan_vectors():
     print("wrote", rv.NAN_NPZ, os.path.getsize(rv.NAN_NPZ), "bytes")
 
 
+def float_class_vectors():
+    """The float-class cases (refvec.FLOAT_GEOMETRIES x float dtypes x
+    methods): tests/float_cases.py's edge frames through the reference, same
+    layout as the main vectors, plus the reference's (w, h, planes) per level
+    as `geometry/<geom>`."""
+    arrays = {}
+    for geom, (dims, n_frames, take) in rv.FLOAT_GEOMETRIES.items():
+        for dt in rv.NAN_DTYPES:
+            dname = np.dtype(dt).name
+            x = rv.make_float_class_inputs(geom, dt)
+            arrays[f"in/{geom}/{dname}"] = x
+            for m in range(4):
+                ds = ref.RefDownsampler(dims, dt, m)
+                arrays[f"geometry/{geom}"] = np.array(ds.geometry, dtype=np.int64)
+                assert [tuple(g) for g in ds.geometry] == rv.FLOAT_LEVELS[geom], ds.geometry
+                ev, out = [], []
+                for k in range(n_frames):
+                    ds.add_frame(x[k])
+                    if not rv.take_now(take, k):
+                        continue
+                    for L in range(1, ds.n_levels):
+                        b = ds.take_bytes(L)
+                        ev.append((k, L, b is not None, 0 if b is None else b.size))
+                        if b is not None:
+                            out.append(b)
+                name = rv.case_name(geom, dt, m)
+                arrays[f"ev/{name}"] = np.array(ev, dtype=np.int64).reshape(-1, 4)
+                arrays[f"out/{name}"] = (np.concatenate(out) if out
+                                         else np.zeros(0, np.uint8))
+    np.savez_compressed(rv.FLOAT_NPZ, **arrays)
+    print("wrote", rv.FLOAT_NPZ, os.path.getsize(rv.FLOAT_NPZ), "bytes")
+
+
 def digests():
     out = {"generator": "tests/digest_util.py (splitmix64, seed 0xA0C2A11 + sorted config index)",
            "digest": "sha256 of each level's taken frames, concatenated in order",
@@ -147,9 +181,14 @@ def main():
     ap.add_argument("--digests", action="store_true", help="also the BASELINE-config digests")
     ap.add_argument("--nan-only", action="store_true",
                     help="only the NaN-payload vectors (reference_nan_vectors.npz)")
+    ap.add_argument("--float-classes", action="store_true",
+                    help="only the float-class vectors (reference_float_classes.npz)")
     a = ap.parse_args()
     if not ref.build():
         sys.exit("oracle/_ref is not built and /root/reference is absent")
+    if a.float_classes:
+        float_class_vectors()
+        return
     nan_vectors()
     if a.nan_only:
         return

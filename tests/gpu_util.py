@@ -59,10 +59,12 @@ def random_frames(rng, dtype, shape, specials=True):
 
 
 def assert_parity(got, want, ctx=""):
-    """Bit-exact for integers; float32/64 within 1 ulp — the tolerance
-    north_star states — with NaNs at the same positions carrying the same bits
-    (the reference binary's payloads).  The kernels are expected to be
-    bit-exact; `exact_fraction` is reported on failure."""
+    """Bit-exact for every dtype.  float32/64 are compared through their
+    integer views, so -0.0 is not +0.0, a neighbouring float is a mismatch and
+    a NaN must carry the same bits (the reference binary's payloads).  On
+    failure the differing values are counted by kind: beyond 1 ulp (a NaN
+    against a number included), exactly 1 ulp, and those that differ only in
+    the sign of zero or in NaN bits."""
     assert got.shape == want.shape, f"{ctx}: shape {got.shape} vs {want.shape}"
     assert got.dtype == want.dtype
     if got.dtype.kind in "ui":
@@ -72,22 +74,26 @@ def assert_parity(got, want, ctx=""):
             raise AssertionError(f"{ctx}: {len(bad)} mismatches, first at {i}: "
                                  f"{got[i]} vs {want[i]}")
         return
-    gn, wn = np.isnan(got), np.isnan(want)
-    assert np.array_equal(gn, wn), f"{ctx}: NaN positions differ"
     ib = np.dtype(f"u{got.dtype.itemsize}")
-    assert np.array_equal(got[gn].view(ib), want[wn].view(ib)), f"{ctx}: NaN payloads differ"
-    g, w = got[~gn], want[~wn]
-    ok = (g == w)
-    if not ok.all():
-        # within one ulp: got is want or one of its two float neighbours
-        up = np.nextafter(w, np.array(np.inf, dtype=w.dtype))
-        dn = np.nextafter(w, np.array(-np.inf, dtype=w.dtype))
-        near = ok | (g == up) | (g == dn)
-        if not near.all():
-            i = int(np.argmin(near))
-            raise AssertionError(f"{ctx}: {int((~near).sum())} values beyond 1 ulp; "
-                                 f"exact fraction {float(ok.mean()):.6f}; first "
-                                 f"{g[i]!r} vs {w[i]!r}")
+    gb, wb = np.ascontiguousarray(got).view(ib), np.ascontiguousarray(want).view(ib)
+    if np.array_equal(gb, wb):
+        return
+    bad = np.argwhere(gb != wb)
+    i = tuple(int(v) for v in bad[0])
+    g, w = got[gb != wb], want[gb != wb]
+    gn, wn = np.isnan(g), np.isnan(w)
+    with np.errstate(invalid="ignore"):
+        sign_or_nan = (gn & wn) | (g == w)      # both NaN, or +0.0 against -0.0
+        one_ulp = ~sign_or_nan & ~gn & ~wn & (
+            (g == np.nextafter(w, np.array(np.inf, dtype=w.dtype))) |
+            (g == np.nextafter(w, np.array(-np.inf, dtype=w.dtype))))
+    beyond = ~sign_or_nan & ~one_ulp
+    raise AssertionError(
+        f"{ctx}: {len(bad)} of {gb.size} values differ in bits (exact fraction "
+        f"{1 - len(bad) / gb.size:.6f}): {int(beyond.sum())} by more than 1 ulp, "
+        f"{int(one_ulp.sum())} by exactly 1 ulp, {int(sign_or_nan.sum())} only in the sign of "
+        f"zero or in NaN bits; first at {i}: {got[i]!r} ({int(gb[i]):#x}) vs "
+        f"{want[i]!r} ({int(wb[i]):#x})")
 
 
 def launch_stream():

@@ -24,7 +24,9 @@ printed:
 and at the end `TOTAL <n> differing` (differing + stray bytes).
 
 The case lists are the smallest shapes at which each scheme triggers,
-imported from the suite's own tables.  Frames per case are capped at
+imported from the suite's own tables.  Frame 0 is gpu_util.random_frames;
+float32 cases of the cascade, tiled and volume families end in
+tests/float_cases.py's edge frames (plant_edge_frames).  Frames per case are capped at
 FRAMES_CAP: the schemes depend on the frame shape, not on the batch length
 beyond "more than one frame".
 """
@@ -87,6 +89,26 @@ def tiled_id(case, method):
 def filter_id(case, shuffle):
     ts, bs, nbytes, nbuf = case
     return f"ts{ts}_bs{bs}_n{nbytes}x{nbuf}/" + {1: "shuffle", 2: "bitshuffle"}[shuffle]
+
+
+def plant_edge_frames(frames, geo):
+    """float32 cases end in tests/float_cases.py's edge frames of the case's
+    shape, so that every launch rule runs the float result classes (the sign
+    of a zero, subnormal rounding, overflow, NaN payloads, zero ties) through
+    its alternative instantiation: the last frame of a 2-D batch, the last
+    half of a one-stack volume (whole Z pairs of every level), the last stack
+    of a longer one.  Frame 0 stays random."""
+    import float_cases as fc
+
+    dt = np.dtype(frames[0].dtype)
+    n = len(frames)
+    if dt != np.float32 or n < 2:
+        return
+    w, h, planes = geo[0]
+    k = 1 if planes == 1 else min(planes, n // 2)
+    edge = fc.edge_frames(dt, planes, h, w, len(geo), planes, geometry=geo)
+    for i in range(1, k + 1):
+        frames[-i][...] = edge[-i]
 
 
 def byte_counts(got, want):
@@ -227,6 +249,7 @@ class Runner:
             for dtype in DTYPES:
                 rng = np.random.default_rng(seed_of("launch-rules", name, dtype_name(dtype)))
                 frames = random_frames(rng, dtype, (n, h, w))
+                plant_edge_frames(frames, geo)
                 bpp = np.dtype(dtype).itemsize
                 # the second pass: the input and every level at a seeded
                 # element offset of 1-7, which turns aligned rows into
@@ -255,6 +278,7 @@ class Runner:
             for dtype in DTYPES:
                 rng = np.random.default_rng(seed_of("launch-rules", name, dtype_name(dtype)))
                 frames = random_frames(rng, dtype, (n, h, w))
+                plant_edge_frames(frames, geo)
                 d_in = to_device(frames)
                 for method in METHODS:
                     expected = oracle_stream(self.oracle, geo, dtype, method, frames)
@@ -275,6 +299,7 @@ class Runner:
             rng = np.random.default_rng(seed_of("launch-rules-tiled", w, h, dtype_name(dt)))
             frames = [random_frames(rng, dt, (h, w)) for _ in range(n)]
             frames[0][: h // 2, : w // 2] = 0  # zero tiles at every level
+            plant_edge_frames(frames, geo)
             for method in METHODS:
                 differing = poison = 0
                 error = None

@@ -171,6 +171,52 @@ def nan_cases():
             for m in range(len(METHOD_NAMES))]
 
 
+# Float-class cases (reference_float_classes.npz): tests/float_cases.py's
+# edge frames, the float dtypes x the four methods, over a 2-D pyramid and an
+# odd stack whose levels halve XY and Z together.  The stack is fed one whole
+# stack of 7 planes, the least that emits both levels' Z pairs and the
+# passed-through last plane.  `geometry/<geom>` holds the reference's own
+# (w, h, planes) per level.
+FLOAT_NPZ = os.path.join(GOLDEN, "reference_float_classes.npz")
+FLOAT_GEOMETRIES = {
+    # 64 x 48 -> 32 x 24 -> 16 x 12 -> 8 x 6
+    "fc_64x48": ([(TIME, 0, 1, 1), (SPACE, 48, 8, 1), (SPACE, 64, 8, 1)], 3, "all"),
+    # [(64, 48, 7), (32, 24, 4), (16, 12, 2)]
+    "fc_stack_64x48x7": ([(TIME, 0, 1, 1), (SPACE, 7, 2, 1), (SPACE, 48, 16, 1),
+                          (SPACE, 64, 16, 1)], 7, "all"),
+}
+# as the reference reports them: the third-from-last dimension of the 2-D
+# array is the append dimension, of size 0
+FLOAT_LEVELS = {"fc_64x48": [(64, 48, 0), (32, 24, 0), (16, 12, 0), (8, 6, 0)],
+                "fc_stack_64x48x7": [(64, 48, 7), (32, 24, 4), (16, 12, 2)]}
+
+
+def float_class_pyramid(geom):
+    """(w, h, planes) per level as tests/float_cases.py takes them."""
+    return [(w, h, max(p, 1)) for w, h, p in FLOAT_LEVELS[geom]]
+
+
+def make_float_class_inputs(geom, dtype):
+    import float_cases as fc
+
+    _, n_frames, _ = FLOAT_GEOMETRIES[geom]
+    geo = float_class_pyramid(geom)
+    w, h, planes = geo[0]
+    return fc.edge_frames(dtype, n_frames, h, w, len(geo), planes, geometry=geo)
+
+
+def float_class_cases():
+    return [(g, np.dtype(d).name, m) for g in FLOAT_GEOMETRIES for d in NAN_DTYPES
+            for m in range(len(METHOD_NAMES))]
+
+
+def float_class_manifest():
+    """The part of a manifest replay() reads, for the float-class cases."""
+    return {"geometries": {g: {"dims": dims, "take": take, "levels": FLOAT_LEVELS[g],
+                               "geometry": [list(x) for x in FLOAT_LEVELS[g]]}
+                           for g, (dims, _, take) in FLOAT_GEOMETRIES.items()}}
+
+
 def load():
     with open(MANIFEST) as f:
         man = json.load(f)

@@ -9,8 +9,9 @@ with one LDS slot per level row).  The fixed geometries in test_gpu_parity.py
 pin each scheme once; these cases sweep widths from 1 to 9000 px, heights
 (1-160) with partial bottom bands, 2-6 levels, all ten dtypes and four methods, and
 input and output buffers at element-aligned but otherwise arbitrary byte
-offsets (which turns aligned rows into misaligned ones).  Integers bit-exact,
-floats within 1 ulp (assert_parity).  Also: chunk-tiled batches with random
+offsets (which turns aligned rows into misaligned ones).  Every dtype
+bit-exact, floats through their integer views (assert_parity).  Also:
+chunk-tiled batches with random
 tile shapes, and Z stacks (fused 2x2x2 or the Z state machine)."""
 import os
 import re

@@ -1,7 +1,7 @@
 """GPU parity: the HIP path (through the C ABI) against the CPU oracle on the
 same seeded inputs, plus the reference's known answers and full-size
-properties.  Integers must be bit-exact; floats within 1 ulp (NaN positions
-equal) — and are additionally checked bit-exact where stated."""
+properties.  Every dtype must be bit-exact: assert_parity compares floats
+through their integer views, the sign of zero and NaN payloads included."""
 import os
 import subprocess
 import zlib
@@ -106,7 +106,8 @@ def test_random_2d_parity(aqz, oracle, dtype, method):
 @pytest.mark.parametrize("method", METHODS)
 def test_float_bit_exact(aqz, oracle, dtype, method):
     """The float path follows the reference's operation order exactly, so it
-    is bit-exact (not merely within 1 ulp), NaN payloads included."""
+    is bit-exact, NaN payloads included (stated here on the integer views,
+    without assert_parity)."""
     rng = np.random.default_rng(5 + method)
     geo = halving_geometry(512, 384, 5)
     frame = random_frames(rng, dtype, (384, 512))

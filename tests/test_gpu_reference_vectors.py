@@ -17,7 +17,9 @@ the ones the reference binary made (x86's first-NaN-operand rule and its
 negative default NaN, restated in ds_kernels.hip's x86_add).  The
 NaN-payload set (reference_nan_vectors.npz: inputs dense in quiet and
 signaling NaNs of both signs and random payloads, and infinities) replays the
-same way.  No reference code runs here — the fixtures travel, the reference
+same way, and so does the float-class set (reference_float_classes.npz:
+tests/float_cases.py's edge frames over a 2-D pyramid and an odd stack).  No
+reference code runs here — the fixtures travel, the reference
 does not.
 """
 import numpy as np
@@ -60,18 +62,43 @@ def test_stream_replays_reference_nan_vectors(aqz, geom, dtype, method):
     _stream_replay(aqz, NAN_VEC, geom, dtype, method)
 
 
+FLOAT_VEC = np.load(rv.FLOAT_NPZ, allow_pickle=False)
+FLOAT_MAN = rv.float_class_manifest()
+FLOAT_CASES = rv.float_class_cases()
+
+
+@pytest.mark.parametrize("geom,dtype,method", FLOAT_CASES,
+                         ids=[f"fc-{g}-{d}-{rv.METHOD_NAMES[m]}" for g, d, m in FLOAT_CASES])
+def test_stream_replays_reference_float_classes(aqz, geom, dtype, method):
+    """tests/float_cases.py's edge frames as the reference itself stored them
+    (reference_float_classes.npz): the sign of zeros, subnormal rounding,
+    overflow and NaN bits, frame by frame."""
+    handles = []
+
+    def make(dims, dt, m):
+        ds = aqz.Downsampler(aqz.level_geometry(aqz.plan_levels(dims)), dt, m)
+        handles.append(ds)
+        return ds
+    try:
+        rv.replay(make, FLOAT_MAN, FLOAT_VEC, geom, dtype, method, nan_bits=True)
+    finally:
+        for ds in handles:
+            ds.close()
+
+
 BATCH_CASES = [("main", g, d, m) for g, d, m in CASES
                if MAN["geometries"][g]["take"] == "all"]
 BATCH_CASES += [("nan", g, d, m) for g, d, m in NAN_CASES
                 if MAN["geometries"][g]["take"] == "all"]
+BATCH_CASES += [("fc", g, d, m) for g, d, m in FLOAT_CASES]
 
 
 @pytest.mark.parametrize("vset,geom,dtype,method", BATCH_CASES,
                          ids=[f"{v}-{g}-{d}-{rv.METHOD_NAMES[m]}" for v, g, d, m in BATCH_CASES])
 def test_device_batch_reproduces_reference_levels(aqz, vset, geom, dtype, method):
     torch = torch_cuda()
-    vec = VEC if vset == "main" else NAN_VEC
-    g = MAN["geometries"][geom]
+    vec = {"main": VEC, "nan": NAN_VEC, "fc": FLOAT_VEC}[vset]
+    g = (FLOAT_MAN if vset == "fc" else MAN)["geometries"][geom]
     dt = np.dtype(dtype)
     frames = vec[f"in/{geom}/{dtype}"]
     name = f"{geom}/{dtype}/{rv.METHOD_NAMES[method]}"
