@@ -57,6 +57,12 @@ EXPORTS = (
     "aqz_node_run_device_batch", "aqz_node_wait_input", "aqz_ds_wait_input",
     "aqz_node_set_level_tiling", "aqz_ds_input_pending", "aqz_node_inputs_released",
     "aqz_debug_launch_log",
+    "aqz_zarr_shard_layout", "aqz_zarr_shard_set_create", "aqz_zarr_shard_set_destroy",
+    "aqz_zarr_shard_set_geometry", "aqz_zarr_shard_set_begin",
+    "aqz_zarr_shard_set_append_layer_device", "aqz_zarr_shard_set_tables_device",
+    "aqz_zarr_shard_set_append_layer", "aqz_zarr_shard_set_tables",
+    "aqz_zarr_shard_chunk_has_data_device", "aqz_debug_zarr_shard_d2h_bytes",
+    "aqz_debug_zarr_shard_set_file_offsets", "aqz_debug_zarr_shard_pack_device",
 )
 
 
@@ -111,6 +117,12 @@ def chunk_frame_offsets(dims, bytes_per_px: int, first_frame: int, n_frames: int
     if rc:
         raise AqzError(rc, lib().aqz_last_error().decode())
     return list(offs)[:n_frames], cb.value, lb.value
+
+
+class ZarrShardGeometry(ctypes.Structure):
+    """aqz_zarr_shard_geometry (include/aqz_shard.h)."""
+    _fields_ = [("n_shards", ctypes.c_uint32), ("chunks_per_shard", ctypes.c_uint32),
+                ("chunks_per_layer", ctypes.c_uint32), ("layers_per_shard", ctypes.c_uint32)]
 
 
 _lib = None
@@ -236,6 +248,25 @@ def lib() -> ctypes.CDLL:
     L.aqz_node_run_device_batch.argtypes = [vp, vp, i32, u32, ctypes.POINTER(vp),
                                             ctypes.POINTER(u32), vp, u32]
     L.aqz_debug_launch_log.argtypes = [ctypes.c_char_p, sz]
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    L.aqz_zarr_shard_layout.argtypes = [ctypes.POINTER(Dimension), u32, u32,
+                                        ctypes.POINTER(ZarrShardGeometry), vp, vp]
+    L.aqz_zarr_shard_set_create.argtypes = [ctypes.POINTER(Dimension), u32, i32,
+                                            ctypes.POINTER(vp)]
+    L.aqz_zarr_shard_set_destroy.argtypes = [vp]
+    L.aqz_zarr_shard_set_destroy.restype = None
+    L.aqz_zarr_shard_set_geometry.argtypes = [vp, ctypes.POINTER(ZarrShardGeometry)]
+    L.aqz_zarr_shard_set_begin.argtypes = [vp, vp]
+    L.aqz_zarr_shard_set_append_layer_device.argtypes = [vp, vp, sz, vp, vp, vp, sz, vp, vp]
+    L.aqz_zarr_shard_set_tables_device.argtypes = [vp, vp, vp, vp]
+    L.aqz_zarr_shard_set_append_layer.argtypes = [vp, vp, sz, vp, vp, vp, sz, vp, vp]
+    L.aqz_zarr_shard_set_tables.argtypes = [vp, vp, vp, vp]
+    L.aqz_zarr_shard_chunk_has_data_device.argtypes = [vp, u32, u32, u32,
+                                                       ctypes.POINTER(u32), vp, vp]
+    L.aqz_debug_zarr_shard_d2h_bytes.argtypes = [vp]
+    L.aqz_debug_zarr_shard_d2h_bytes.restype = ctypes.c_uint64
+    L.aqz_debug_zarr_shard_set_file_offsets.argtypes = [vp, u64p, vp]
+    L.aqz_debug_zarr_shard_pack_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, u32, i32, vp, vp]
     _lib = L
     return L
 
@@ -808,6 +839,141 @@ def crc32c_device(device_data: int, nbytes: int, stride: int, n_buffers: int,
                              ctypes.c_void_p(stream) if stream else None)
     if rc:
         raise AqzError(rc, L.aqz_last_error().decode())
+
+
+ZARR_SHARD_SENTINEL = 0xFFFFFFFFFFFFFFFF  # aqz_shard.h
+ZARR_SHARD_PACK_PIECE = 64 << 10  # kShardPackPiece, csrc/shard_kernels.hh
+
+
+def _dim_array(dims):
+    return (Dimension * max(len(dims), 1))(*[Dimension(d[0], d[1], d[2], d[3], 1.0)
+                                             for d in dims])
+
+
+def zarr_shard_layout(dims, layer_in_shard: int = 0):
+    """aqz_zarr_shard_layout for storage-order `dims` = [(type, array_size,
+    chunk_size, shard_size_chunks), ...]: (geometry dict, shard_of,
+    internal_of), the two as uint32 arrays over the layer's chunks.  Host
+    only, no GPU involved."""
+    arr = _dim_array(dims)
+    geo = ZarrShardGeometry()
+    L = lib()
+    rc = L.aqz_zarr_shard_layout(arr, len(dims), layer_in_shard, ctypes.byref(geo), None, None)
+    if rc:
+        raise AqzError(rc, "zarr_shard_layout: bad dimensions or layer")
+    shard_of = np.empty(geo.chunks_per_layer, np.uint32)
+    internal_of = np.empty(geo.chunks_per_layer, np.uint32)
+    rc = L.aqz_zarr_shard_layout(arr, len(dims), layer_in_shard, ctypes.byref(geo),
+                                 shard_of.ctypes.data, internal_of.ctypes.data)
+    if rc:
+        raise AqzError(rc, "zarr_shard_layout: bad dimensions or layer")
+    g = {k: getattr(geo, k) for k, _ in ZarrShardGeometry._fields_}
+    return g, shard_of, internal_of
+
+
+def zarr_shard_chunk_has_data_device(device_tile_nonzero: int, n_frames: int, n_tiles: int,
+                                     flag_slots: int, frame_chunk_base, device_has_data: int,
+                                     stream: int = 0):
+    """aqz_zarr_shard_chunk_has_data_device (asynchronous on `stream`)."""
+    base = (ctypes.c_uint32 * max(n_frames, 1))(*[int(b) for b in frame_chunk_base])
+    _raise_if(lib().aqz_zarr_shard_chunk_has_data_device(
+        device_tile_nonzero, n_frames, n_tiles, flag_slots, base, device_has_data,
+        ctypes.c_void_p(stream) if stream else None))
+
+
+class ZarrShardSet:
+    """aqz_zarr_shard_set: the Zarr v3 shards of one array on one device
+    (Shard::write_chunk / skip_chunk / write_table_, shard.cpp:53-165, driven
+    like Array::compress_and_flush_data_, array.cpp:762-811)."""
+
+    def __init__(self, dims, device: int = 0):
+        h = ctypes.c_void_p()
+        _raise_if(lib().aqz_zarr_shard_set_create(_dim_array(dims), len(dims), device,
+                                                  ctypes.byref(h)))
+        self._h = h
+        geo = ZarrShardGeometry()
+        _raise_if(lib().aqz_zarr_shard_set_geometry(h, ctypes.byref(geo)))
+        self.n_shards = geo.n_shards
+        self.chunks_per_shard = geo.chunks_per_shard
+        self.chunks_per_layer = geo.chunks_per_layer
+        self.layers_per_shard = geo.layers_per_shard
+        self.table_bytes = 16 * geo.chunks_per_shard + 4
+        self.segment_words = 3 * geo.n_shards + 1
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().aqz_zarr_shard_set_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def begin(self, stream: int = 0):
+        _raise_if(lib().aqz_zarr_shard_set_begin(self._h,
+                                                 ctypes.c_void_p(stream) if stream else None))
+
+    def append_layer_device(self, device_frames: int, frame_stride: int, device_out: int,
+                            out_capacity: int, device_segments: int,
+                            device_frame_bytes: int = 0, device_has_data: int = 0,
+                            stream: int = 0):
+        """aqz_zarr_shard_set_append_layer_device: queued on `stream`, nothing
+        crosses to the host."""
+        _raise_if(lib().aqz_zarr_shard_set_append_layer_device(
+            self._h, device_frames, frame_stride, device_frame_bytes or None,
+            device_has_data or None, device_out, out_capacity, device_segments,
+            ctypes.c_void_p(stream) if stream else None))
+
+    def tables_device(self, device_tables: int, device_table_offsets: int, stream: int = 0):
+        _raise_if(lib().aqz_zarr_shard_set_tables_device(
+            self._h, device_tables, device_table_offsets,
+            ctypes.c_void_p(stream) if stream else None))
+
+    def append_layer(self, device_frames: int, frame_stride: int, device_frame_bytes: int = 0,
+                     device_has_data: int = 0, stream: int = 0, host_out=None):
+        """aqz_zarr_shard_set_append_layer: (segment rows as an (n_shards, 3)
+        uint64 array of start / bytes / file offset, total, host bytes)."""
+        cap = self.chunks_per_layer * frame_stride
+        if host_out is None:
+            host_out = np.empty(max(cap, 1), np.uint8)
+        seg = np.empty(self.segment_words, np.uint64)
+        _raise_if(lib().aqz_zarr_shard_set_append_layer(
+            self._h, device_frames, frame_stride, device_frame_bytes or None,
+            device_has_data or None, host_out.ctypes.data, host_out.nbytes, seg.ctypes.data,
+            ctypes.c_void_p(stream) if stream else None))
+        total = int(seg[-1])
+        return seg[:-1].reshape(-1, 3), total, host_out[:total]
+
+    def tables(self, stream: int = 0):
+        """aqz_zarr_shard_set_tables: (tables as an (n_shards, table_bytes)
+        uint8 array, their file offsets)."""
+        tab = np.empty((self.n_shards, self.table_bytes), np.uint8)
+        off = np.empty(self.n_shards, np.uint64)
+        _raise_if(lib().aqz_zarr_shard_set_tables(
+            self._h, tab.ctypes.data, off.ctypes.data,
+            ctypes.c_void_p(stream) if stream else None))
+        return tab, off
+
+    def d2h_bytes(self) -> int:
+        """Bytes the last append_layer copied from device to host."""
+        return lib().aqz_debug_zarr_shard_d2h_bytes(self._h)
+
+    def debug_set_file_offsets(self, offsets, stream: int = 0):
+        arr = (ctypes.c_uint64 * self.n_shards)(*[int(o) for o in offsets])
+        _raise_if(lib().aqz_debug_zarr_shard_set_file_offsets(
+            self._h, arr, ctypes.c_void_p(stream) if stream else None))
+
+    def debug_pack_device(self, device_frames: int, frame_stride: int, device_out: int,
+                          device_segments: int, piece_bytes: int, policy: int = 0,
+                          device_frame_bytes: int = 0, device_has_data: int = 0,
+                          device_offsets: int = 0, stream: int = 0):
+        """aqz_debug_zarr_shard_pack_device (A/B timing only)."""
+        _raise_if(lib().aqz_debug_zarr_shard_pack_device(
+            self._h, device_frames, frame_stride, device_frame_bytes or None,
+            device_has_data or None, device_out, device_segments or None, piece_bytes, policy,
+            device_offsets or None, ctypes.c_void_p(stream) if stream else None))
 
 
 def alg_bytes_per_frame(geometry, bpp: int) -> int:
