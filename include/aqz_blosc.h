@@ -76,7 +76,12 @@ int aqz_blosc_frame_from_filtered(int clevel,
  * aqz_blosc_compress_device.  n_threads 0: min(16, hardware threads).
  * A ctx serves one call at a time: its scratch is shared by every call on
  * it, so two threads must not use one ctx concurrently (one ctx per thread,
- * as the reference's compression jobs would hold one each). */
+ * as the reference's compression jobs would hold one each).  The ctx orders
+ * nothing itself: calls queued on one stream follow each other by stream
+ * order, and a caller that queues aqz_blosc_lz4_frames_device on a second
+ * stream while a call on the first may still run must order the two itself
+ * (an event recorded behind the first call and waited for by the second
+ * stream). */
 typedef struct aqz_blosc_ctx aqz_blosc_ctx;
 
 int aqz_blosc_ctx_create(int device, uint32_t n_threads, aqz_blosc_ctx** out);
@@ -124,7 +129,9 @@ int aqz_blosc_compress_device(aqz_blosc_ctx* ctx,
 
 /* filter + LZ4 + frame, all on hip_stream, no synchronisation: frame k at
  * device_dst + k * dst_stride (dst_stride >= nbytes + 16), its size in
- * device_frame_bytes[k]. lz4 only. Scratch grows inside ctx. */
+ * device_frame_bytes[k]. lz4 only. Scratch grows inside ctx: only a call
+ * that needs more of it than any before (the first, or one of more bytes)
+ * frees and reallocates, which waits for the device. */
 int aqz_blosc_lz4_frames_device(aqz_blosc_ctx* ctx,
                                 int clevel,
                                 int shuffle,

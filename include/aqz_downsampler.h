@@ -439,8 +439,10 @@ int aqz_ds_run_device_batch(aqz_ds* ds,
  * `out_counts` as for aqz_ds_run_device_batch.  Pyramids deeper than 4
  * levels chain runs through handle scratch, so each tiled/chunked batch is
  * ordered behind the handle's previous one whatever stream either ran on
- * (an event wait; no host synchronisation).  A handle is not thread-safe:
- * one caller thread at a time, as for zarr::Downsampler.
+ * (an event wait; no host synchronisation).  Only the call that grows that
+ * scratch — the first deep batch, or one of more frames than any before —
+ * waits for `hip_stream` to drain before it reallocates.  A handle is not
+ * thread-safe: one caller thread at a time, as for zarr::Downsampler.
  */
 int aqz_ds_run_device_batch_tiled(aqz_ds* ds,
                                   const void* device_frames,
@@ -490,8 +492,13 @@ typedef struct
  * chunk).  A frame whose tiles would leave the lattice buffer, an offset or
  * stride that is not a multiple of the pixel size, or a stride below one
  * tile is AQZ_INVALID_ARGUMENT before anything runs.  The offsets cross to
- * the device on `hip_stream` with the batch; the call returns without
- * synchronising, and `lattices` may be freed on return.
+ * the device on `hip_stream` with the batch, through one of two pinned
+ * staging halves the handle owns, and `lattices` may be freed on return.
+ * At most two chunked batches of a handle are in flight: a call returns
+ * without synchronising while the batch two calls back has finished, else it
+ * waits on the host for that batch (not for the one just before it), because
+ * it rewrites the half that batch's upload reads.  A call that needs a larger
+ * offset table than any before waits for both and reallocates.
  */
 int aqz_ds_run_device_batch_chunked(aqz_ds* ds,
                                     const void* device_frames,
@@ -694,7 +701,10 @@ int aqz_node_run_host_batch(aqz_node* node,
  * pyramid and push overlap.  Asynchronous: the blocks start behind the work
  * already on `hip_stream` (NULL = the null stream of `src_device`), and
  * `hip_stream` waits for every block before its later work runs; the call
- * returns without a host synchronisation.  `flags`: 0 or AQZ_NODE_STAGE_ALL.
+ * returns without a host synchronisation (only a call whose blocks need more
+ * staging than any before drains the handle's three streams and reallocates;
+ * adds in flight are waited for, as said above).  `flags`: 0 or
+ * AQZ_NODE_STAGE_ALL.
  * The caller's current device is unchanged on return.
  */
 int aqz_node_run_device_batch(aqz_node* node,

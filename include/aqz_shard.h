@@ -77,7 +77,11 @@ int aqz_zarr_shard_layout(const aqz_dimension* dims,
  * (offset, extent) uint64 pairs (offsets_ / extents_), and the slot map
  * (shard, slot j) -> chunk c of a layer or none, uploaded once: a layer only
  * adds layer_in_shard * S to the slot number to get the internal index.
- * A set serves one call at a time.
+ * A set serves one call at a time.  It orders nothing itself: begin, the
+ * layers and the tables queued on one stream follow each other by stream
+ * order; a caller that moves to another stream while earlier calls may still
+ * run must order the two itself (an event recorded behind the earlier calls
+ * and waited for by the new stream).
  * Refused with AQZ_OVERFLOW at create: what aqz_zarr_shard_layout refuses,
  * and an index table of 1 GiB or more (aqz_crc32c_device's limit).
  */

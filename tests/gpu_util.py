@@ -98,7 +98,9 @@ def assert_parity(got, want, ctx=""):
 
 def launch_stream():
     """A non-null torch stream handle for the batch API (NULL would select the
-    handle's own stream)."""
+    handle's own stream).  It synchronises the device first, so a test that
+    uses it hands the library an idle stream and complete inputs and cannot
+    see a stream-ordering mistake; tests/test_gpu_stream_order.py does."""
     torch = torch_cuda()
     torch.cuda.synchronize()  # inputs were produced on the previous stream
     s = torch.cuda.Stream()
