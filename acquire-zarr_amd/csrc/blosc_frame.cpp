@@ -809,22 +809,10 @@ aqz_blosc_compress_device(aqz_blosc_ctx* ctx, int clevel, int shuffle, uint32_t 
         }
 
         const size_t total = nbytes * n_buffers;
-        if (ctx->d_cap < total) {
-            if (ctx->d_filtered)
-                BLOSC_HIP(hipFree(ctx->d_filtered), "free");
-            ctx->d_filtered = nullptr;
-            ctx->d_cap = 0;
-            BLOSC_HIP(hipMalloc(&ctx->d_filtered, total), "device scratch");
-            ctx->d_cap = total;
-        }
-        if (ctx->h_cap < total) {
-            if (ctx->h_filtered)
-                BLOSC_HIP(hipHostFree(ctx->h_filtered), "free pinned");
-            ctx->h_filtered = nullptr;
-            ctx->h_cap = 0;
-            BLOSC_HIP(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_filtered), total), "pinned staging");
-            ctx->h_cap = total;
-        }
+        if (const int rc = grow_device(&ctx->d_filtered, &ctx->d_cap, total); rc != AQZ_OK)
+            return rc;
+        if (const int rc = grow_pinned(&ctx->h_filtered, &ctx->h_cap, total); rc != AQZ_OK)
+            return rc;
         // groups of about 4 MiB cross PCIe one after another; the host
         // compresses a group as soon as its copy has landed
         const uint32_t per_group =

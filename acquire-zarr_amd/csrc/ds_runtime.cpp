@@ -18,6 +18,7 @@
 #include "aqz_downsampler.h"
 #include "abi_guard.hh"
 #include "ds_kernels.hh"
+#include "hip_raii.hh"
 
 #include <hip/hip_runtime.h>
 
@@ -96,105 +97,138 @@ env_flag(const char* name)
 
 struct aqz_ds
 {
+    // One pyramid level's streaming state (level 0 uses the descriptor,
+    // `bytes` and `count` only).
+    struct Level
+    {
+        aqz_level_desc desc{};
+        size_t bytes = 0;     // bytes of one frame
+        bool xy = false;      // halves XY (L >= 1)
+        bool zh = false;      // halves Z (L >= 1)
+        uint32_t count = 0;   // level_frame_count_
+        bool has_partial = false;
+        // aqz_ds_add_frame_async_take with AQZ_TAKE_HOLD: the caller still
+        // holds an untaken frame of the level, so new ones are dropped (the
+        // emplace rule, downsampler.cpp:599-605) as if it were cached here
+        bool held = false;
+
+        aqz::DeviceBuf slot[2];    // two result slots
+        aqz::DeviceBuf d_partial;  // stored earlier plane (Z levels)
+        aqz::PinnedBuf h_level;    // eager readback: pinned copy of the frame
+        bool no_eager = false;     // level taken tiled: that copy would be wasted
+
+        // aqz_ds_set_level_tiling: the tile shape (0,0: off) and two tiled
+        // slots paired with `slot`.  `flags` is pinned and kernel-written;
+        // its capacity is what the half can hold, `slices` the flag bytes per
+        // tile of the frame tiled there (tile_slices for the tile kernel,
+        // cascade_tiled_slots for the one-pass tiled cascade).
+        uint32_t tile_rows = 0, tile_cols = 0;
+        struct Tiled
+        {
+            aqz::DeviceBuf tiles;
+            aqz::PinnedBuf flags;
+            uint32_t slices = 1;
+        } tiled[2];
+        aqz::PinnedBuf h_tiles; // eager readback: pinned copy of the tiles
+
+        uint64_t elems() const { return uint64_t(desc.width) * desc.height; }
+
+        // What has been done to the untaken frame.  cached_ is the slot that
+        // holds it (-1: none).  The other three name the slot whose frame
+        // tiled[k] (tiled_for_), h_level (host_for_) and h_tiles (htile_for_)
+        // hold.  Invariant: each of the three is -1 or equal to cached_, so
+        // nothing derived from a frame outlives it.  Only the members below
+        // write them.
+        int cached() const { return cached_; }
+        bool is_tiled() const { return cached_ >= 0 && tiled_for_ == cached_; }
+        bool on_host() const { return cached_ >= 0 && host_for_ == cached_; }
+        bool tiles_on_host() const { return cached_ >= 0 && htile_for_ == cached_; }
+        // where a new frame is written: never the cached slot
+        int free_slot() const { return cached_ == 0 ? 1 : 0; }
+        void cache(int k) { cached_ = k; }
+        void mark_tiled() { tiled_for_ = cached_; }
+        void mark_on_host() { host_for_ = cached_; }
+        void mark_tiles_on_host() { htile_for_ = cached_; }
+        void drop_tiled() { tiled_for_ = htile_for_ = -1; } // the tiling changed
+        void drop_cached() { cached_ = tiled_for_ = host_for_ = htile_for_ = -1; }
+
+      private:
+        int cached_ = -1, tiled_for_ = -1, host_for_ = -1, htile_for_ = -1;
+    };
+
+    // Member order is destruction order reversed.  The streams come first, so
+    // every buffer and event below is destroyed before the stream it was used
+    // on; inside Pipe likewise.  release() synchronises `stream`, both
+    // lattice_done events and chain_done before it deletes the handle, so
+    // nothing is freed under queued work.
+    aqz::Stream own_stream;
+    hipStream_t stream = nullptr; // own_stream, or a batch caller's (StreamSwap)
+
+    // aqz_ds_run_host_batch pipeline, allocated on first use
+    struct Pipe
+    {
+        aqz::Stream s_in, s_work, s_out;
+        uint32_t group = 0;                  // frames per group the buffers hold
+        aqz::DeviceBuf d_in[2];
+        std::vector<aqz::DeviceBuf> d_out[2]; // per level, group-sized
+        aqz::Event in_done[2], work_done[2], out_done[2];
+    } pipe;
+
     int device = 0;
     int dtype = 0;
     int method = 0;
     size_t bpp = 0;
     uint32_t n = 0;
-    std::vector<aqz_level_desc> lv;
-    std::vector<size_t> bytes;      // bytes of one frame per level
-    std::vector<uint8_t> xy;        // level L halves XY (L >= 1)
-    std::vector<uint8_t> zh;        // level L halves Z (L >= 1)
-    std::vector<uint32_t> count;    // level_frame_count_
-    std::vector<uint8_t> has_partial;
-    // aqz_ds_add_frame_async_take with AQZ_TAKE_HOLD: the caller still holds
-    // an untaken frame of the level, so new ones are dropped (the emplace
-    // rule, downsampler.cpp:599-605) as if it were cached here
-    std::vector<uint8_t> held;
+    std::vector<Level> lv;
 
-    hipStream_t stream = nullptr;
-    void* d_in = nullptr;                      // level-0 frame on device
-    std::vector<std::pair<void*, void*>> slot; // two output slots per level
-    std::vector<int> cached;                   // slot holding the untaken frame, -1 none
-    std::vector<void*> d_partial;              // stored earlier plane (Z levels)
-    hipEvent_t h2d_done = nullptr;
+    aqz::DeviceBuf d_in; // level-0 frame on device
+    aqz::Event h2d_done;
     // orders a caller's stream against `stream` around a batch run on it
-    hipEvent_t join = nullptr;
+    aqz::Event join;
     // optional pinned staging of host frames ($AQZ_PINNED_STAGING=1)
     bool staged = false;
-    void* h_stage = nullptr;
+    aqz::PinnedBuf h_stage;
     size_t device_bytes = 0;
     int last_batch_kind = -1;
 
     // Small pyramids (all levels together <= kEagerBytes): every newly cached
-    // level frame is copied to pinned host memory right behind the kernels,
-    // so the take_frame calls that follow cost one event wait and a memcpy
-    // each instead of a device round trip each ($AQZ_EAGER_READBACK=0: off).
+    // level frame is copied to pinned host memory (Level::h_level) right
+    // behind the kernels, so the take_frame calls that follow cost one event
+    // wait and a memcpy each instead of a device round trip each
+    // ($AQZ_EAGER_READBACK=0: off).  With level tiling the tiles are copied
+    // instead (Level::h_tiles), queued right behind their tile kernel.
     bool eager = false;
-    std::vector<uint8_t*> h_level;  // pinned copy per level
-    std::vector<int> host_for;      // slot whose frame h_level holds, -1 none
-    std::vector<uint8_t> no_eager;  // level taken tiled: the host copy would be wasted
-    hipEvent_t levels_d2h = nullptr;
+    aqz::Event levels_d2h;
 
-    // aqz_ds_take_frame_tiled: on-demand scratch (tiles, then slice flags)
-    void* d_tiles = nullptr;
-    size_t d_tiles_bytes = 0;
+    // aqz_ds_take_frame_tiled: on-demand scratch (tiles, and pinned slice flags)
+    aqz::DeviceBuf d_tiles;
+    aqz::PinnedBuf h_flags;
     // aqz_ds_run_device_batch_tiled: row-major copy of the last level of a
     // fused run that feeds the next run (pyramids deeper than 4 XY levels)
-    void* d_chain = nullptr;
-    size_t d_chain_bytes = 0;
+    aqz::DeviceBuf d_chain;
     // recorded after every tiled batch: the next one (on any stream) waits on
     // it before it rewrites d_chain
-    hipEvent_t chain_done = nullptr;
+    aqz::Event chain_done;
     // aqz_ds_run_device_batch_chunked: per-level frame offsets (elements),
     // staged in pinned memory and copied to the device on the batch's
     // stream; two halves used by alternate calls, each guarded by the event
     // recorded after the batch that read it
-    uint64_t* d_lattice = nullptr;
-    uint64_t* h_lattice = nullptr;
-    size_t lattice_half = 0; // entries per half
+    aqz::DeviceBuf d_lattice;
+    aqz::PinnedBuf h_lattice;
     uint32_t lattice_calls = 0;
-    hipEvent_t lattice_done[2] = { nullptr, nullptr };
-    // aqz_ds_set_level_tiling: per level (tile_rows, tile_cols), two tiled
-    // slots (tiles then slice flags) paired with `slot`, and which slot's
-    // frame they currently hold (-1 none)
-    std::vector<std::pair<uint32_t, uint32_t>> tiling;
-    std::vector<std::pair<void*, void*>> tslot;
-    std::vector<std::pair<uint8_t*, uint8_t*>> tflags; // pinned, kernel-written
-    // per level and tiled slot: flag bytes each half can hold, and the flag
-    // bytes per tile of the frame tiled there (tile_slices for the tile
-    // kernel, cascade_tiled_slots for the one-pass tiled cascade)
-    std::vector<std::array<size_t, 2>> tflag_cap;
-    std::vector<std::array<uint32_t, 2>> tflag_slices;
-    std::vector<int> tiled_for;
+    aqz::Event lattice_done[2];
     // $AQZ_STREAM_TILE_PASS=1: eager tiling as a tile pass behind the
     // row-major cascade (the round-2 path), for A/B
     bool tile_pass = false;
     uint64_t stream_tiled_runs = 0; // runs the streaming path tiled in one launch
-    // eager tiled readback (aqz_ds::eager): pinned copy of a level's tiles,
-    // queued right behind its tile kernel, and which slot's frame it holds
-    std::vector<uint8_t*> h_tiles;
-    std::vector<int> htile_for;
-    uint8_t* h_flags = nullptr; // pinned slice flags for on-demand tiling
-    size_t h_flags_bytes = 0;
 
     // aqz_ds_set_input_transpose: input frames arrive in acquisition order
     // (rows = level-0 width) and are transposed into d_tin on the device
     bool transpose = false;
-    void* d_tin = nullptr;
+    aqz::DeviceBuf d_tin;
     // the last level-0 frame added (storage order), for aqz_ds_take_input_frame;
     // null once taken or after a batch
     const void* last_input = nullptr;
-
-    // aqz_ds_run_host_batch pipeline, allocated on first use
-    struct Pipe
-    {
-        uint32_t group = 0;                  // frames per group
-        hipStream_t s_in = nullptr, s_work = nullptr, s_out = nullptr;
-        void* d_in[2] = { nullptr, nullptr };
-        std::vector<void*> d_out[2];         // per level, group-sized
-        hipEvent_t in_done[2] = {}, work_done[2] = {}, out_done[2] = {};
-    } pipe;
 
     // aqz_ds_add_frame_async: one worker thread (started on first use) runs
     // at most one pending add_frame; every other entry point settles it first
@@ -224,12 +258,6 @@ struct aqz_ds
         err = what;
         return AQZ_INVALID_ARGUMENT;
     }
-    void* slot_ptr(uint32_t L, int k) const
-    {
-        return k == 0 ? slot[L].first : slot[L].second;
-    }
-    // where a new level-L frame is written: never the cached slot
-    void* out_slot(uint32_t L) const { return slot_ptr(L, cached[L] == 0 ? 1 : 0); }
 };
 
 namespace aqz {
@@ -261,25 +289,54 @@ struct Sink
     std::vector<uint32_t>* emitted = nullptr;
 };
 
-uint64_t
-elems(const aqz_ds* ds, uint32_t level)
-{
-    return uint64_t(ds->lv[level].width) * ds->lv[level].height;
-}
+using Level = aqz_ds::Level;
 
-// Tiled layout of level L at (tr, tc): tile bytes and slice-flag bytes.
+// Tiled layout of a level at (tr, tc): tile bytes and slice-flag bytes.
 struct TileGeom
 {
     size_t n_tiles, tile_bytes, flag_bytes;
 };
 
 TileGeom
-tile_geom(const aqz_ds* ds, uint32_t L, uint32_t tr, uint32_t tc)
+tile_geom(const aqz_ds* ds, const Level& lv, uint32_t tr, uint32_t tc)
 {
-    const aqz_level_desc& lv = ds->lv[L];
-    const size_t ntx = (lv.width + tc - 1) / tc, nty = (lv.height + tr - 1) / tr;
+    const size_t ntx = (lv.desc.width + tc - 1) / tc, nty = (lv.desc.height + tr - 1) / tr;
     const size_t nt = ntx * nty;
     return { nt, nt * tr * tc * ds->bpp, nt * aqz::tile_slices(tr, tc) };
+}
+
+// LevelOut[] of the run of levels L..L+k-1, level l written at ptr_of(l).
+template<class PtrOf>
+void
+fill_outs(const aqz_ds* ds, uint32_t L, uint32_t k, PtrOf ptr_of, aqz::LevelOut* outs)
+{
+    for (uint32_t j = 0; j < k; ++j) {
+        const Level& lv = ds->lv[L + j];
+        outs[j] = { ptr_of(L + j), lv.elems(), lv.desc.width, lv.desc.height };
+    }
+}
+
+// XY-reduce `n_frames` frames at `src` (level L-1) into the run `outs`: the
+// fused cascade where the planner takes the run (*fused), else one generic
+// launch per level.
+hipError_t
+launch_xy_run(const aqz_ds* ds, const void* src, uint32_t L, uint32_t k,
+              const aqz::LevelOut* outs, uint32_t n_frames, hipStream_t stream, bool* fused)
+{
+    const Level& a = ds->lv[L - 1];
+    *fused = aqz::cascade_supported(ds->dtype, src, a.elems(), a.desc.width, a.desc.height, outs,
+                                    int(k));
+    if (*fused)
+        return aqz::launch_cascade(ds->dtype, ds->method, src, a.elems(), a.desc.width,
+                                   a.desc.height, outs, int(k), n_frames, stream);
+    hipError_t e = hipSuccess;
+    for (uint32_t j = 0; j < k && e == hipSuccess; ++j) {
+        const Level& in = ds->lv[L + j - 1];
+        e = aqz::launch_xy_generic(ds->dtype, ds->method, src, in.elems(), in.desc.width,
+                                   in.desc.height, outs[j], n_frames, stream);
+        src = outs[j].ptr;
+    }
+    return e;
 }
 
 // One flag per tile: the OR of its `slices` flag bytes (pinned,
@@ -315,27 +372,16 @@ int
 tile_to_host(aqz_ds* ds, const void* d_frame, const aqz_level_desc& lv, uint32_t tile_rows,
              uint32_t tile_cols, const TileGeom& g, void* dst, uint8_t* tile_nonzero)
 {
-    if (ds->d_tiles_bytes < g.tile_bytes) {
-        (void)hipFree(ds->d_tiles);
-        ds->d_tiles = nullptr;
-        ds->d_tiles_bytes = 0;
-        HIP_TRY(ds, hipMalloc(&ds->d_tiles, g.tile_bytes), "hipMalloc tiles");
-        ds->d_tiles_bytes = g.tile_bytes;
-    }
-    if (ds->h_flags_bytes < g.flag_bytes) {
-        (void)hipHostFree(ds->h_flags);
-        ds->h_flags = nullptr;
-        ds->h_flags_bytes = 0;
-        HIP_TRY(ds, hipHostMalloc(reinterpret_cast<void**>(&ds->h_flags), g.flag_bytes,
-                                  hipHostMallocDefault), "hipHostMalloc flags");
-        ds->h_flags_bytes = g.flag_bytes;
-    }
+    // every earlier use of the scratch was waited for (tiles_to_host)
+    HIP_TRY(ds, ds->d_tiles.reserve(g.tile_bytes), "hipMalloc tiles");
+    HIP_TRY(ds, ds->h_flags.reserve(g.flag_bytes), "hipHostMalloc flags");
     HIP_TRY(ds,
             aqz::launch_tile_frame_sliced(ds->dtype, d_frame, lv.width, lv.height, tile_rows,
-                                          tile_cols, ds->d_tiles, ds->h_flags, ds->stream),
+                                          tile_cols, ds->d_tiles.get(), ds->h_flags.bytes(),
+                                          ds->stream),
             "tile kernel");
-    return tiles_to_host(ds, g, g.flag_bytes / g.n_tiles, ds->d_tiles, ds->h_flags, dst,
-                         tile_nonzero);
+    return tiles_to_host(ds, g, g.flag_bytes / g.n_tiles, ds->d_tiles.get(),
+                         ds->h_flags.bytes(), dst, tile_nonzero);
 }
 
 // Working buffer for a level-L result: the caller's batch slot when the
@@ -343,10 +389,10 @@ tile_to_host(aqz_ds* ds, const void* d_frame, const aqz_level_desc& lv, uint32_t
 void*
 level_target(aqz_ds* ds, uint32_t L, const Sink& sink)
 {
+    const Level& lv = ds->lv[L];
     if (sink.batch)
-        return static_cast<uint8_t*>(sink.out[L]) +
-               (*sink.emitted)[L] * ds->bytes[L];
-    return ds->out_slot(L);
+        return static_cast<uint8_t*>(sink.out[L]) + (*sink.emitted)[L] * lv.bytes;
+    return lv.slot[lv.free_slot()].get();
 }
 
 // emplace_downsampled_frame_ (downsampler.cpp:599-605).  `pretiled`: the
@@ -355,12 +401,12 @@ level_target(aqz_ds* ds, uint32_t L, const Sink& sink)
 int
 emit(aqz_ds* ds, uint32_t level, const void* d_frame, const Sink& sink, bool pretiled = false)
 {
-    ++ds->count[level];
+    Level& lv = ds->lv[level];
+    ++lv.count;
     void* want = level_target(ds, level, sink);
     if (want != d_frame) {
         HIP_TRY(ds,
-                hipMemcpyAsync(want, d_frame, ds->bytes[level],
-                               hipMemcpyDeviceToDevice, ds->stream),
+                hipMemcpyAsync(want, d_frame, lv.bytes, hipMemcpyDeviceToDevice, ds->stream),
                 "hipMemcpyAsync D2D");
     }
     if (sink.batch) {
@@ -369,23 +415,22 @@ emit(aqz_ds* ds, uint32_t level, const void* d_frame, const Sink& sink, bool pre
     }
     // unordered_map::emplace keeps an untaken frame; the new one is dropped
     // (it stays in the free slot only as the next level's input).
-    if (ds->cached[level] < 0 && !ds->held[level]) {
-        const int k = (want == ds->slot[level].first) ? 0 : 1;
-        ds->cached[level] = k;
-        const auto [tr, tc] = ds->tiling[level];
+    if (lv.cached() < 0 && !lv.held) {
+        const int k = lv.free_slot(); // `want` is that slot
+        lv.cache(k);
+        const uint32_t tr = lv.tile_rows, tc = lv.tile_cols;
         if (tr && pretiled) {
-            ds->tiled_for[level] = k;
+            lv.mark_tiled();
         } else if (tr) {
             // queue the chunk tiling right behind the pyramid (§8(f) row 2)
-            void* tb = k == 0 ? ds->tslot[level].first : ds->tslot[level].second;
-            uint8_t* fb = k == 0 ? ds->tflags[level].first : ds->tflags[level].second;
+            Level::Tiled& t = lv.tiled[k];
             HIP_TRY(ds,
-                    aqz::launch_tile_frame_sliced(ds->dtype, want, ds->lv[level].width,
-                                                  ds->lv[level].height, tr, tc, tb, fb,
+                    aqz::launch_tile_frame_sliced(ds->dtype, want, lv.desc.width, lv.desc.height,
+                                                  tr, tc, t.tiles.get(), t.flags.bytes(),
                                                   ds->stream),
                     "tile kernel");
-            ds->tiled_for[level] = k;
-            ds->tflag_slices[level][k] = aqz::tile_slices(tr, tc);
+            lv.mark_tiled();
+            t.slices = aqz::tile_slices(tr, tc);
         }
     }
     return AQZ_OK;
@@ -404,49 +449,40 @@ launch_run_tiled(aqz_ds* ds, uint32_t L, uint32_t k, const void* cur,
     *launched = false;
     if (ds->tile_pass)
         return AQZ_OK;
-    const aqz_level_desc& a = ds->lv[L - 1];
-    if (aqz::cascade_tiled_cols(ds->dtype, a.width) !=
-        aqz::cascade_pick_cols(ds->dtype, cur, elems(ds, L - 1), a.width, a.height, outs, int(k)))
+    const Level& a = ds->lv[L - 1];
+    if (aqz::cascade_tiled_cols(ds->dtype, a.desc.width) !=
+        aqz::cascade_pick_cols(ds->dtype, cur, a.elems(), a.desc.width, a.desc.height, outs,
+                               int(k)))
         return AQZ_OK;
     aqz::TiledOut t[aqz::kMaxFusedLevels];
     uint32_t slices[aqz::kMaxFusedLevels];
-    int kk[aqz::kMaxFusedLevels];
     for (uint32_t j = 0; j < k; ++j) {
-        const uint32_t l = L + j;
-        const auto [tr, tc] = ds->tiling[l];
+        Level& lv = ds->lv[L + j];
+        const uint32_t tr = lv.tile_rows, tc = lv.tile_cols;
         if (!tr)
             return AQZ_OK;
-        const int s = outs[j].ptr == ds->slot[l].first ? 0 : 1;
-        const uint32_t slots = aqz::cascade_tiled_slots(ds->dtype, a.width, int(k), int(j + 1),
-                                                        tr, tc, nullptr);
-        if (!slots)
+        slices[j] = aqz::cascade_tiled_slots(ds->dtype, a.desc.width, int(k), int(j + 1), tr, tc,
+                                             nullptr);
+        if (!slices[j])
             return AQZ_OK; // one OR-ed flag per tile would need a clear of pinned memory
-        slices[j] = slots;
-        const TileGeom g = tile_geom(ds, l, tr, tc);
-        const size_t need = g.n_tiles * slices[j];
-        uint8_t*& fb = s == 0 ? ds->tflags[l].first : ds->tflags[l].second;
-        if (ds->tflag_cap[l][s] < need) {
-            // the half is free (its slot is not the cached one); earlier
-            // kernels may still write it
+        // outs[j] is the level's free slot: its tiled half is free too
+        Level::Tiled& half = lv.tiled[lv.free_slot()];
+        const size_t need = tile_geom(ds, lv, tr, tc).n_tiles * slices[j];
+        if (half.flags.capacity() < need) {
+            // earlier kernels may still write the half
             HIP_TRY(ds, hipStreamSynchronize(ds->stream), "hipStreamSynchronize");
-            (void)hipHostFree(fb);
-            fb = nullptr;
-            ds->tflag_cap[l][s] = 0;
-            HIP_TRY(ds, hipHostMalloc(reinterpret_cast<void**>(&fb), need, hipHostMallocDefault),
-                    "hipHostMalloc flags");
-            ds->tflag_cap[l][s] = need;
+            HIP_TRY(ds, half.flags.reserve(need), "hipHostMalloc flags");
         }
-        kk[j] = s;
-        t[j] = { s == 0 ? ds->tslot[l].first : ds->tslot[l].second, tr, tc, fb };
+        t[j] = { half.tiles.get(), tr, tc, half.flags.bytes() };
     }
-    const hipError_t e = aqz::launch_cascade_tiled(ds->dtype, ds->method, cur, elems(ds, L - 1),
-                                                   a.width, a.height, outs, t, int(k), 1,
-                                                   ds->stream);
+    const hipError_t e = aqz::launch_cascade_tiled(ds->dtype, ds->method, cur, a.elems(),
+                                                   a.desc.width, a.desc.height, outs, t, int(k),
+                                                   1, ds->stream);
     if (e == hipErrorInvalidValue)
         return AQZ_OK;
     HIP_TRY(ds, e, "tiled cascade kernel");
     for (uint32_t j = 0; j < k; ++j)
-        ds->tflag_slices[L + j][kk[j]] = slices[j];
+        ds->lv[L + j].tiled[ds->lv[L + j].free_slot()].slices = slices[j];
     ++ds->stream_tiled_runs;
     *launched = true;
     return AQZ_OK;
@@ -456,16 +492,10 @@ launch_run_tiled(aqz_ds* ds, uint32_t L, uint32_t k, const void* cur,
 int
 reduce_xy(aqz_ds* ds, uint32_t L, const void* src, void* dst)
 {
-    const aqz_level_desc& a = ds->lv[L - 1];
-    aqz::LevelOut o{ dst, elems(ds, L), ds->lv[L].width, ds->lv[L].height };
-    hipError_t e;
-    if (aqz::cascade_supported(ds->dtype, src, elems(ds, L - 1), a.width, a.height, &o, 1))
-        e = aqz::launch_cascade(ds->dtype, ds->method, src, elems(ds, L - 1),
-                                a.width, a.height, &o, 1, 1, ds->stream);
-    else
-        e = aqz::launch_xy_generic(ds->dtype, ds->method, src, elems(ds, L - 1),
-                                   a.width, a.height, o, 1, ds->stream);
-    HIP_TRY(ds, e, "xy level kernel");
+    aqz::LevelOut o;
+    fill_outs(ds, L, 1, [&](uint32_t) { return dst; }, &o);
+    bool fused;
+    HIP_TRY(ds, launch_xy_run(ds, src, L, 1, &o, 1, ds->stream, &fused), "xy level kernel");
     return AQZ_OK;
 }
 
@@ -474,46 +504,28 @@ reduce_xy(aqz_ds* ds, uint32_t L, const void* src, void* dst)
 int
 process_frame(aqz_ds* ds, const void* d_frame, const Sink& sink)
 {
-    ++ds->count[0];
+    ++ds->lv[0].count;
     const void* cur = d_frame;
     uint32_t L = 1;
     while (L < ds->n) {
-        if (ds->xy[L] && !ds->zh[L]) {
+        Level& lv = ds->lv[L];
+        if (lv.xy && !lv.zh) {
             // Run of pure-XY levels: they always emit, fuse up to 4.
             uint32_t k = 1;
-            while (L + k < ds->n && k < aqz::kMaxFusedLevels && ds->xy[L + k] &&
-                   !ds->zh[L + k])
+            while (L + k < ds->n && k < aqz::kMaxFusedLevels && ds->lv[L + k].xy &&
+                   !ds->lv[L + k].zh)
                 ++k;
             aqz::LevelOut outs[aqz::kMaxFusedLevels];
-            for (uint32_t j = 0; j < k; ++j)
-                outs[j] = { level_target(ds, L + j, sink), elems(ds, L + j),
-                            ds->lv[L + j].width, ds->lv[L + j].height };
-            const aqz_level_desc& a = ds->lv[L - 1];
+            fill_outs(ds, L, k, [&](uint32_t l) { return level_target(ds, l, sink); }, outs);
             bool pretiled = false;
             if (!sink.batch)
                 if (int rc = launch_run_tiled(ds, L, k, cur, outs, &pretiled))
                     return rc;
-            if (pretiled) {
-                // levels and their tiles written by the tiled cascade
-            } else if (aqz::cascade_supported(ds->dtype, cur, elems(ds, L - 1), a.width,
-                                              a.height, outs, int(k))) {
-                HIP_TRY(ds,
-                        aqz::launch_cascade(ds->dtype, ds->method, cur,
-                                            elems(ds, L - 1), a.width, a.height,
-                                            outs, int(k), 1, ds->stream),
-                        "cascade kernel");
-            } else {
-                const void* s = cur;
-                for (uint32_t j = 0; j < k; ++j) {
-                    const aqz_level_desc& b = ds->lv[L + j - 1];
-                    HIP_TRY(ds,
-                            aqz::launch_xy_generic(ds->dtype, ds->method, s,
-                                                   elems(ds, L + j - 1), b.width,
-                                                   b.height, outs[j], 1,
-                                                   ds->stream),
-                            "xy level kernel");
-                    s = outs[j].ptr;
-                }
+            // pretiled: levels and their tiles written by the tiled cascade
+            if (!pretiled) {
+                bool fused;
+                const hipError_t e = launch_xy_run(ds, cur, L, k, outs, 1, ds->stream, &fused);
+                HIP_TRY(ds, e, fused ? "cascade kernel" : "xy level kernel");
             }
             for (uint32_t j = 0; j < k; ++j) {
                 int rc = emit(ds, L + j, outs[j].ptr, sink, pretiled);
@@ -526,30 +538,30 @@ process_frame(aqz_ds* ds, const void* d_frame, const Sink& sink)
         }
 
         // General level: optional XY reduce, then optional Z pairing.
-        const uint32_t prev_planes = ds->lv[L - 1].planes;
-        bool average = ds->zh[L] != 0;
-        if (prev_planes % 2 != 0 && ds->count[L - 1] % prev_planes == 0)
+        const uint32_t prev_planes = ds->lv[L - 1].desc.planes;
+        bool average = lv.zh;
+        if (prev_planes % 2 != 0 && ds->lv[L - 1].count % prev_planes == 0)
             average = false; // last plane of an odd stack passes through
 
-        if (average && !ds->has_partial[L]) {
+        if (average && !lv.has_partial) {
             // store this plane as the earlier half of the pair, then stop
-            if (ds->xy[L]) {
-                int rc = reduce_xy(ds, L, cur, ds->d_partial[L]);
+            if (lv.xy) {
+                int rc = reduce_xy(ds, L, cur, lv.d_partial.get());
                 if (rc)
                     return rc;
             } else {
                 HIP_TRY(ds,
-                        hipMemcpyAsync(ds->d_partial[L], cur, ds->bytes[L],
+                        hipMemcpyAsync(lv.d_partial.get(), cur, lv.bytes,
                                        hipMemcpyDeviceToDevice, ds->stream),
                         "hipMemcpyAsync D2D");
             }
-            ds->has_partial[L] = 1;
+            lv.has_partial = true;
             break;
         }
 
         void* target = level_target(ds, L, sink);
         const void* next = cur;
-        if (ds->xy[L]) {
+        if (lv.xy) {
             int rc = reduce_xy(ds, L, cur, target);
             if (rc)
                 return rc;
@@ -558,11 +570,10 @@ process_frame(aqz_ds* ds, const void* d_frame, const Sink& sink)
         if (average) {
             // average_two_frames(dst = earlier, src = current)
             HIP_TRY(ds,
-                    aqz::launch_zpair(ds->dtype, ds->method, target,
-                                      ds->d_partial[L], next, elems(ds, L),
-                                      ds->stream),
+                    aqz::launch_zpair(ds->dtype, ds->method, target, lv.d_partial.get(), next,
+                                      lv.elems(), ds->stream),
                     "zpair kernel");
-            ds->has_partial[L] = 0;
+            lv.has_partial = false;
             next = target;
         }
         int rc = emit(ds, L, next, sink);
@@ -584,9 +595,9 @@ bind_device(aqz_ds* ds)
 int
 check_host_frame(aqz_ds* ds, const void* host_frame, size_t nbytes, const char* who)
 {
-    if (!host_frame || nbytes != ds->bytes[0])
+    if (!host_frame || nbytes != ds->lv[0].bytes)
         return ds->fail_arg(std::string(who) + ": expected " +
-                            std::to_string(ds->bytes[0]) + " bytes, got " +
+                            std::to_string(ds->lv[0].bytes) + " bytes, got " +
                             std::to_string(nbytes));
     return AQZ_OK;
 }
@@ -601,10 +612,10 @@ process_input(aqz_ds* ds, const void* d_frame)
     if (ds->transpose) {
         // acquisition rows = storage width (array.dimensions.cpp:578-599)
         HIP_TRY(ds,
-                aqz::launch_transpose(ds->dtype, d_frame, ds->lv[0].width,
-                                      ds->lv[0].height, ds->d_tin, ds->stream),
+                aqz::launch_transpose(ds->dtype, d_frame, ds->lv[0].desc.width,
+                                      ds->lv[0].desc.height, ds->d_tin.get(), ds->stream),
                 "transpose kernel");
-        d_frame = ds->d_tin;
+        d_frame = ds->d_tin.get();
     }
     ds->last_input = d_frame;
     return process_frame(ds, d_frame, Sink{});
@@ -622,31 +633,31 @@ eager_readback(aqz_ds* ds)
         return AQZ_OK;
     bool any = false;
     for (uint32_t L = 1; L < ds->n; ++L) {
-        const int k = ds->cached[L];
+        Level& lv = ds->lv[L];
+        const int k = lv.cached();
         if (k < 0)
             continue;
-        if (ds->no_eager[L]) {
+        if (lv.no_eager) {
             // taken tiled: copy the tiles out instead, so the D2H overlaps
             // whatever the caller does before take_frame_tiled
-            if (ds->h_tiles[L] && ds->tiled_for[L] == k && ds->htile_for[L] != k) {
-                const TileGeom g = tile_geom(ds, L, ds->tiling[L].first, ds->tiling[L].second);
-                void* tb = k == 0 ? ds->tslot[L].first : ds->tslot[L].second;
+            if (lv.h_tiles && lv.is_tiled() && !lv.tiles_on_host()) {
+                const TileGeom g = tile_geom(ds, lv, lv.tile_rows, lv.tile_cols);
                 HIP_TRY(ds,
-                        hipMemcpyAsync(ds->h_tiles[L], tb, g.tile_bytes, hipMemcpyDeviceToHost,
-                                       ds->stream),
+                        hipMemcpyAsync(lv.h_tiles.get(), lv.tiled[k].tiles.get(), g.tile_bytes,
+                                       hipMemcpyDeviceToHost, ds->stream),
                         "hipMemcpyAsync D2H (eager tiles)");
-                ds->htile_for[L] = k;
+                lv.mark_tiles_on_host();
                 any = true;
             }
             continue;
         }
-        if (ds->host_for[L] == k)
+        if (lv.on_host())
             continue;
         HIP_TRY(ds,
-                hipMemcpyAsync(ds->h_level[L], ds->slot_ptr(L, k), ds->bytes[L],
+                hipMemcpyAsync(lv.h_level.get(), lv.slot[k].get(), lv.bytes,
                                hipMemcpyDeviceToHost, ds->stream),
                 "hipMemcpyAsync D2H (eager)");
-        ds->host_for[L] = k;
+        lv.mark_on_host();
         any = true;
     }
     if (any)
@@ -659,18 +670,18 @@ add_host_frame(aqz_ds* ds, const void* host_frame)
 {
     if (int rc = bind_device(ds))
         return rc;
-    const size_t nbytes = ds->bytes[0];
+    const size_t nbytes = ds->lv[0].bytes;
     const void* src = host_frame;
     if (ds->staged) {
         // previous upload must be done before the staging buffer is reused
         HIP_TRY(ds, hipEventSynchronize(ds->h2d_done), "hipEventSynchronize");
-        std::memcpy(ds->h_stage, host_frame, nbytes);
-        src = ds->h_stage;
+        std::memcpy(ds->h_stage.get(), host_frame, nbytes);
+        src = ds->h_stage.get();
     }
     // Straight from the caller's (pageable) frame: the copy engine reads it
     // at full PCIe rate, no host staging memcpy (tools/e2e_probe.cpp).
     HIP_TRY(ds,
-            hipMemcpyAsync(ds->d_in, src, nbytes, hipMemcpyHostToDevice, ds->stream),
+            hipMemcpyAsync(ds->d_in.get(), src, nbytes, hipMemcpyHostToDevice, ds->stream),
             "hipMemcpyAsync H2D");
     // From here on the copy may still read the caller's frame: every way out
     // waits for it first, so that a failed add, too, releases the frame only
@@ -679,7 +690,7 @@ add_host_frame(aqz_ds* ds, const void* host_frame)
         (void)hipStreamSynchronize(ds->stream);
         return ds->fail(e, "hipEventRecord");
     }
-    int rc = process_input(ds, ds->d_in);
+    int rc = process_input(ds, ds->d_in.get());
     if (rc == AQZ_OK)
         rc = eager_readback(ds);
     if (rc != AQZ_OK) {
@@ -701,33 +712,31 @@ take_plain(aqz_ds* ds, uint32_t level, void* dst, size_t cap, size_t* nbytes, in
     *has_frame = 0;
     if (level == 0 || level >= ds->n)
         return AQZ_OK; // the reference's map lookup simply misses
-    if (ds->cached[level] < 0)
+    Level& lv = ds->lv[level];
+    if (lv.cached() < 0)
         return AQZ_OK;
     *has_frame = 1;
     if (nbytes)
-        *nbytes = ds->bytes[level];
+        *nbytes = lv.bytes;
     if (!dst)
         return AQZ_OK;
-    if (cap < ds->bytes[level])
+    if (cap < lv.bytes)
         return ds->fail_arg("take_frame: buffer too small");
     if (int rc = bind_device(ds))
         return rc;
-    if (ds->eager && ds->host_for[level] == ds->cached[level]) {
+    if (ds->eager && lv.on_host()) {
         // already on its way to pinned memory (eager_readback)
         HIP_TRY(ds, hipEventSynchronize(ds->levels_d2h), "hipEventSynchronize");
-        std::memcpy(dst, ds->h_level[level], ds->bytes[level]);
+        std::memcpy(dst, lv.h_level.get(), lv.bytes);
     } else {
         // HBM -> caller memory directly (stream-ordered after the kernels)
         HIP_TRY(ds,
-                hipMemcpyAsync(dst, ds->slot_ptr(level, ds->cached[level]),
-                               ds->bytes[level], hipMemcpyDeviceToHost, ds->stream),
+                hipMemcpyAsync(dst, lv.slot[lv.cached()].get(), lv.bytes, hipMemcpyDeviceToHost,
+                               ds->stream),
                 "hipMemcpyAsync D2H");
         HIP_TRY(ds, hipStreamSynchronize(ds->stream), "hipStreamSynchronize");
     }
-    ds->cached[level] = -1;
-    ds->tiled_for[level] = -1;
-    ds->host_for[level] = -1;
-    ds->htile_for[level] = -1;
+    lv.drop_cached();
     return AQZ_OK;
 }
 
@@ -746,9 +755,10 @@ take_tiled(aqz_ds* ds,
     *has_frame = 0;
     if (tile_rows == 0 || tile_cols == 0)
         return ds->fail_arg("take_frame_tiled: empty tile");
-    if (level == 0 || level >= ds->n || ds->cached[level] < 0)
+    if (level == 0 || level >= ds->n || ds->lv[level].cached() < 0)
         return AQZ_OK;
-    const TileGeom g = tile_geom(ds, level, tile_rows, tile_cols);
+    Level& lv = ds->lv[level];
+    const TileGeom g = tile_geom(ds, lv, tile_rows, tile_cols);
     *has_frame = 1;
     if (nbytes)
         *nbytes = g.tile_bytes;
@@ -758,33 +768,25 @@ take_tiled(aqz_ds* ds,
         return ds->fail_arg("take_frame_tiled: buffer too small");
     if (int rc = bind_device(ds))
         return rc;
-    const int k = ds->cached[level];
-    if (ds->tiling[level] == std::make_pair(tile_rows, tile_cols) &&
-        ds->tiled_for[level] == k && ds->htile_for[level] == k) {
+    const Level::Tiled& t = lv.tiled[lv.cached()];
+    const bool pretiled = lv.tile_rows == tile_rows && lv.tile_cols == tile_cols && lv.is_tiled();
+    if (pretiled && lv.tiles_on_host()) {
         // tiled and copied out when the frame was emitted (eager readback)
         HIP_TRY(ds, hipEventSynchronize(ds->levels_d2h), "hipEventSynchronize");
-        std::memcpy(dst, ds->h_tiles[level], g.tile_bytes);
+        std::memcpy(dst, lv.h_tiles.get(), g.tile_bytes);
         if (tile_nonzero)
-            reduce_slice_flags(g, ds->tflag_slices[level][k],
-                               k == 0 ? ds->tflags[level].first : ds->tflags[level].second,
-                               tile_nonzero);
-    } else if (ds->tiling[level] == std::make_pair(tile_rows, tile_cols) &&
-               ds->tiled_for[level] == k) {
+            reduce_slice_flags(g, t.slices, t.flags.bytes(), tile_nonzero);
+    } else if (pretiled) {
         // tiled when the frame was emitted (aqz_ds_set_level_tiling)
-        if (int rc = tiles_to_host(ds, g, ds->tflag_slices[level][k],
-                                   k == 0 ? ds->tslot[level].first : ds->tslot[level].second,
-                                   k == 0 ? ds->tflags[level].first : ds->tflags[level].second,
-                                   dst, tile_nonzero))
+        if (int rc = tiles_to_host(ds, g, t.slices, t.tiles.get(), t.flags.bytes(), dst,
+                                   tile_nonzero))
             return rc;
-    } else if (int rc = tile_to_host(ds, ds->slot_ptr(level, k), ds->lv[level], tile_rows,
+    } else if (int rc = tile_to_host(ds, lv.slot[lv.cached()].get(), lv.desc, tile_rows,
                                      tile_cols, g, dst, tile_nonzero)) {
         return rc;
     }
-    ds->cached[level] = -1;
-    ds->tiled_for[level] = -1;
-    ds->host_for[level] = -1;
-    ds->htile_for[level] = -1;
-    ds->no_eager[level] = 1; // this caller takes the level tiled
+    lv.drop_cached();
+    lv.no_eager = true; // this caller takes the level tiled
     return AQZ_OK;
 }
 
@@ -845,6 +847,14 @@ async_worker(aqz_ds* ds)
     }
 }
 
+// A plain add: the caller holds no untaken frame (Level::held).
+void
+release_holds(aqz_ds* ds)
+{
+    for (Level& lv : ds->lv)
+        lv.held = false;
+}
+
 // Wait for a pending aqz_ds_add_frame_async; returns (and clears) its status.
 int
 settle(aqz_ds* ds)
@@ -873,65 +883,16 @@ release(aqz_ds* ds)
         ds->async.cv.notify_all();
         ds->async.worker.join();
     }
-    // Best-effort teardown: errors here have nowhere to go.
+    // Best-effort teardown: errors here have nowhere to go.  Everything the
+    // handle owns frees itself (see the member order in aqz_ds) once the
+    // work that may still use it is done.
     (void)hipSetDevice(ds->device);
     if (ds->stream)
         (void)hipStreamSynchronize(ds->stream);
-    (void)hipFree(ds->d_in);
-    for (auto& s : ds->slot) {
-        (void)hipFree(s.first);
-        (void)hipFree(s.second);
-    }
-    for (void* p : ds->d_partial)
-        (void)hipFree(p);
-    (void)hipHostFree(ds->h_stage);
-    (void)hipFree(ds->d_tiles);
-    for (hipEvent_t e : ds->lattice_done)
-        if (e) {
+    for (hipEvent_t e : { ds->lattice_done[0].get(), ds->lattice_done[1].get(),
+                          ds->chain_done.get() })
+        if (e)
             (void)hipEventSynchronize(e);
-            (void)hipEventDestroy(e);
-        }
-    (void)hipFree(ds->d_lattice);
-    (void)hipHostFree(ds->h_lattice);
-    if (ds->chain_done) {
-        (void)hipEventSynchronize(ds->chain_done);
-        (void)hipEventDestroy(ds->chain_done);
-    }
-    (void)hipFree(ds->d_chain);
-    for (auto& t : ds->tslot) {
-        (void)hipFree(t.first);
-        (void)hipFree(t.second);
-    }
-    for (auto& t : ds->tflags) {
-        (void)hipHostFree(t.first);
-        (void)hipHostFree(t.second);
-    }
-    (void)hipHostFree(ds->h_flags);
-    for (uint8_t* h : ds->h_level)
-        (void)hipHostFree(h);
-    for (uint8_t* h : ds->h_tiles)
-        (void)hipHostFree(h);
-    if (ds->levels_d2h)
-        (void)hipEventDestroy(ds->levels_d2h);
-    (void)hipFree(ds->d_tin);
-    if (ds->h2d_done)
-        (void)hipEventDestroy(ds->h2d_done);
-    if (ds->join)
-        (void)hipEventDestroy(ds->join);
-    for (int b = 0; b < 2; ++b) {
-        (void)hipFree(ds->pipe.d_in[b]);
-        for (void* p : ds->pipe.d_out[b])
-            (void)hipFree(p);
-        for (hipEvent_t e : { ds->pipe.in_done[b], ds->pipe.work_done[b],
-                              ds->pipe.out_done[b] })
-            if (e)
-                (void)hipEventDestroy(e);
-    }
-    for (hipStream_t st : { ds->pipe.s_in, ds->pipe.s_work, ds->pipe.s_out })
-        if (st)
-            (void)hipStreamDestroy(st);
-    if (ds->stream)
-        (void)hipStreamDestroy(ds->stream);
     delete ds;
 }
 
@@ -1153,37 +1114,24 @@ aqz_ds_create(const aqz_level_desc* levels,
         ds->method = method;
         ds->bpp = aqz::dtype_bytes(dtype);
         ds->n = n_levels;
-        ds->lv.assign(levels, levels + n_levels);
-        ds->bytes.resize(n_levels);
-        ds->xy.assign(n_levels, 0);
-        ds->zh.assign(n_levels, 0);
-        ds->count.assign(n_levels, 0);
-        ds->has_partial.assign(n_levels, 0);
-        ds->slot.assign(n_levels, { nullptr, nullptr });
-        ds->cached.assign(n_levels, -1);
-        ds->d_partial.assign(n_levels, nullptr);
+        ds->lv = std::vector<Level>(n_levels);
         ds->staged = env_flag("AQZ_PINNED_STAGING");
-        ds->tiling.assign(n_levels, { 0, 0 });
-        ds->tslot.assign(n_levels, { nullptr, nullptr });
-        ds->held.assign(n_levels, 0);
-        ds->tflags.assign(n_levels, { nullptr, nullptr });
-        ds->tflag_cap.assign(n_levels, { 0, 0 });
-        ds->tflag_slices.assign(n_levels, { 1, 1 });
         ds->tile_pass = env_flag("AQZ_STREAM_TILE_PASS");
-        ds->tiled_for.assign(n_levels, -1);
-        ds->h_tiles.assign(n_levels, nullptr);
-        ds->htile_for.assign(n_levels, -1);
-        ds->h_level.assign(n_levels, nullptr);
-        ds->host_for.assign(n_levels, -1);
-        ds->no_eager.assign(n_levels, 0);
+        size_t level_total = 0;
         for (uint32_t l = 0; l < n_levels; ++l) {
-            ds->bytes[l] = size_t(levels[l].width) * levels[l].height * ds->bpp;
+            Level& lv = ds->lv[l];
+            lv.desc = levels[l];
+            lv.bytes = size_t(levels[l].width) * levels[l].height * ds->bpp;
             if (l > 0) {
-                ds->xy[l] = levels[l].width < levels[l - 1].width ||
-                            levels[l].height < levels[l - 1].height;
-                ds->zh[l] = levels[l].planes < levels[l - 1].planes;
+                lv.xy = levels[l].width < levels[l - 1].width ||
+                        levels[l].height < levels[l - 1].height;
+                lv.zh = levels[l].planes < levels[l - 1].planes;
+                level_total += lv.bytes;
             }
         }
+        const char* eager_env = std::getenv("AQZ_EAGER_READBACK");
+        ds->eager = n_levels > 1 && level_total <= kEagerBytes &&
+                    !(eager_env && std::strcmp(eager_env, "0") == 0);
 
         auto fail = [&](hipError_t e, const char* what) {
             const int code = e == hipErrorOutOfMemory ? AQZ_OUT_OF_MEMORY
@@ -1192,48 +1140,37 @@ aqz_ds_create(const aqz_level_desc* levels,
             release(ds);
             return code;
         };
-        hipError_t e = hipSetDevice(device);
-        if (e != hipSuccess)
-            return fail(e, "hipSetDevice");
-        if ((e = hipStreamCreateWithFlags(&ds->stream, hipStreamNonBlocking)) != hipSuccess)
-            return fail(e, "hipStreamCreate");
-        if ((e = hipEventCreateWithFlags(&ds->h2d_done, hipEventDisableTiming)) != hipSuccess)
-            return fail(e, "hipEventCreate");
-        if ((e = hipEventCreateWithFlags(&ds->join, hipEventDisableTiming)) != hipSuccess)
-            return fail(e, "hipEventCreate");
-        if ((e = hipMalloc(&ds->d_in, ds->bytes[0])) != hipSuccess)
-            return fail(e, "hipMalloc level 0");
-        size_t level_total = 0;
-        for (uint32_t l = 1; l < n_levels; ++l)
-            level_total += ds->bytes[l];
-        const char* eager_env = std::getenv("AQZ_EAGER_READBACK");
-        ds->eager = n_levels > 1 && level_total <= kEagerBytes &&
-                    !(eager_env && std::strcmp(eager_env, "0") == 0);
+    #define CREATE_TRY(expr, what)                                                 \
+        do {                                                                       \
+            if (const hipError_t e_ = (expr); e_ != hipSuccess)                    \
+                return fail(e_, what);                                             \
+        } while (0)
+        CREATE_TRY(hipSetDevice(device), "hipSetDevice");
+        CREATE_TRY(ds->own_stream.create(), "hipStreamCreate");
+        ds->stream = ds->own_stream;
+        CREATE_TRY(ds->h2d_done.create(), "hipEventCreate");
+        CREATE_TRY(ds->join.create(), "hipEventCreate");
+        CREATE_TRY(ds->d_in.reserve(ds->lv[0].bytes), "hipMalloc level 0");
         if (ds->eager) {
-            if ((e = hipEventCreateWithFlags(&ds->levels_d2h, hipEventDisableTiming)) !=
-                hipSuccess)
-                return fail(e, "hipEventCreate");
+            CREATE_TRY(ds->levels_d2h.create(), "hipEventCreate");
             for (uint32_t l = 1; l < n_levels; ++l)
-                if ((e = hipHostMalloc(reinterpret_cast<void**>(&ds->h_level[l]), ds->bytes[l],
-                                       hipHostMallocDefault)) != hipSuccess)
-                    return fail(e, "hipHostMalloc level copy");
+                CREATE_TRY(ds->lv[l].h_level.reserve(ds->lv[l].bytes),
+                           "hipHostMalloc level copy");
         }
-        if (ds->staged &&
-            (e = hipHostMalloc(&ds->h_stage, ds->bytes[0], hipHostMallocDefault)) != hipSuccess)
-            return fail(e, "hipHostMalloc staging");
-        ds->device_bytes = ds->bytes[0];
+        if (ds->staged)
+            CREATE_TRY(ds->h_stage.reserve(ds->lv[0].bytes), "hipHostMalloc staging");
+        ds->device_bytes = ds->lv[0].bytes;
         for (uint32_t l = 1; l < n_levels; ++l) {
-            if ((e = hipMalloc(&ds->slot[l].first, ds->bytes[l])) != hipSuccess)
-                return fail(e, "hipMalloc level");
-            if ((e = hipMalloc(&ds->slot[l].second, ds->bytes[l])) != hipSuccess)
-                return fail(e, "hipMalloc level");
-            ds->device_bytes += 2 * ds->bytes[l];
-            if (ds->zh[l]) {
-                if ((e = hipMalloc(&ds->d_partial[l], ds->bytes[l])) != hipSuccess)
-                    return fail(e, "hipMalloc partial");
-                ds->device_bytes += ds->bytes[l];
+            Level& lv = ds->lv[l];
+            CREATE_TRY(lv.slot[0].reserve(lv.bytes), "hipMalloc level");
+            CREATE_TRY(lv.slot[1].reserve(lv.bytes), "hipMalloc level");
+            ds->device_bytes += 2 * lv.bytes;
+            if (lv.zh) {
+                CREATE_TRY(lv.d_partial.reserve(lv.bytes), "hipMalloc partial");
+                ds->device_bytes += lv.bytes;
             }
         }
+    #undef CREATE_TRY
         *out = ds;
         return AQZ_OK;
     } catch (...) {
@@ -1261,7 +1198,7 @@ aqz_ds_add_frame(aqz_ds* ds, const void* host_frame, size_t nbytes)
             return rc;
         if (int rc = check_host_frame(ds, host_frame, nbytes, "add_frame"))
             return rc;
-        std::fill(ds->held.begin(), ds->held.end(), 0);
+        release_holds(ds);
         return add_host_frame(ds, host_frame);
     } catch (...) {
         return ABI_GUARD_FAIL(ds);
@@ -1278,7 +1215,7 @@ aqz_ds_add_frame_async(aqz_ds* ds, const void* host_frame, size_t nbytes)
             return rc;
         if (int rc = check_host_frame(ds, host_frame, nbytes, "add_frame_async"))
             return rc;
-        std::fill(ds->held.begin(), ds->held.end(), 0);
+        release_holds(ds);
         auto& a = ds->async;
         if (!a.worker.joinable())
             a.worker = std::thread(async_worker, ds);
@@ -1313,16 +1250,16 @@ aqz_ds_add_frame_async_take(aqz_ds* ds,
                 ((t.tile_rows == 0) != (t.tile_cols == 0)))
                 return ds->fail_arg("add_frame_async_take: level " + std::to_string(L) +
                                     ": bad mode or tile shape");
-            if (t.mode == AQZ_TAKE_HOLD && ds->cached[L] >= 0)
+            if (t.mode == AQZ_TAKE_HOLD && ds->lv[L].cached() >= 0)
                 return ds->fail_arg("add_frame_async_take: level " + std::to_string(L) +
                                     " is held by the caller but also cached here");
             // every take buffer is checked before the job is queued, so the
             // background takes cannot fail half way and leave a level taken
             // (uncached here) that the caller never learns about
             if (t.mode == AQZ_TAKE_INTO) {
-                const size_t need = t.tile_rows
-                                      ? tile_geom(ds, L, t.tile_rows, t.tile_cols).tile_bytes
-                                      : ds->bytes[L];
+                const Level& lv = ds->lv[L];
+                const size_t need =
+                  t.tile_rows ? tile_geom(ds, lv, t.tile_rows, t.tile_cols).tile_bytes : lv.bytes;
                 if (!t.dst || t.cap < need)
                     return ds->fail_arg("add_frame_async_take: level " + std::to_string(L) +
                                         ": take buffer missing or smaller than " +
@@ -1330,7 +1267,7 @@ aqz_ds_add_frame_async_take(aqz_ds* ds,
             }
         }
         for (uint32_t L = 1; L < ds->n; ++L)
-            ds->held[L] = takes[L].mode == AQZ_TAKE_HOLD;
+            ds->lv[L].held = takes[L].mode == AQZ_TAKE_HOLD;
         auto& a = ds->async;
         if (!a.worker.joinable())
             a.worker = std::thread(async_worker, ds);
@@ -1420,11 +1357,11 @@ aqz_ds_add_device_frame(aqz_ds* ds, const void* device_frame, size_t nbytes)
             return AQZ_INVALID_ARGUMENT;
         if (int rc = settle(ds))
             return rc;
-        if (!device_frame || nbytes != ds->bytes[0])
+        if (!device_frame || nbytes != ds->lv[0].bytes)
             return ds->fail_arg("add_device_frame: expected " +
-                                std::to_string(ds->bytes[0]) + " bytes, got " +
+                                std::to_string(ds->lv[0].bytes) + " bytes, got " +
                                 std::to_string(nbytes));
-        std::fill(ds->held.begin(), ds->held.end(), 0);
+        release_holds(ds);
         if (int rc = bind_device(ds))
             return rc;
         if (int rc = process_input(ds, device_frame))
@@ -1470,38 +1407,28 @@ aqz_ds_set_level_tiling(aqz_ds* ds, uint32_t level, uint32_t tile_rows, uint32_t
         if (int rc = bind_device(ds))
             return rc;
         HIP_TRY(ds, hipStreamSynchronize(ds->stream), "hipStreamSynchronize");
-        auto& t = ds->tslot[level];
-        (void)hipFree(t.first);
-        (void)hipFree(t.second);
-        t = { nullptr, nullptr };
-        auto& tf = ds->tflags[level];
-        (void)hipHostFree(tf.first);
-        (void)hipHostFree(tf.second);
-        tf = { nullptr, nullptr };
-        ds->tflag_cap[level] = { 0, 0 };
-        (void)hipHostFree(ds->h_tiles[level]);
-        ds->h_tiles[level] = nullptr;
-        ds->htile_for[level] = -1;
-        ds->tiling[level] = { 0, 0 };
-        ds->tiled_for[level] = -1;
-        ds->no_eager[level] = tile_rows != 0;
+        Level& lv = ds->lv[level];
+        for (Level::Tiled& t : lv.tiled) {
+            t.tiles.reset();
+            t.flags.reset();
+        }
+        lv.h_tiles.reset();
+        lv.tile_rows = lv.tile_cols = 0;
+        lv.drop_tiled();
+        lv.no_eager = tile_rows != 0;
         if (tile_rows == 0)
             return AQZ_OK;
-        const TileGeom g = tile_geom(ds, level, tile_rows, tile_cols);
-        HIP_TRY(ds, hipMalloc(&t.first, g.tile_bytes), "hipMalloc tiles");
-        HIP_TRY(ds, hipMalloc(&t.second, g.tile_bytes), "hipMalloc tiles");
+        const TileGeom g = tile_geom(ds, lv, tile_rows, tile_cols);
+        for (Level::Tiled& t : lv.tiled)
+            HIP_TRY(ds, t.tiles.reserve(g.tile_bytes), "hipMalloc tiles");
         // slice flags live in pinned host memory the kernel writes directly, so
         // take_frame_tiled needs no separate flag copy
-        HIP_TRY(ds, hipHostMalloc(reinterpret_cast<void**>(&tf.first), g.flag_bytes,
-                                  hipHostMallocDefault), "hipHostMalloc flags");
-        HIP_TRY(ds, hipHostMalloc(reinterpret_cast<void**>(&tf.second), g.flag_bytes,
-                                  hipHostMallocDefault), "hipHostMalloc flags");
-        ds->tflag_cap[level] = { g.flag_bytes, g.flag_bytes };
+        for (Level::Tiled& t : lv.tiled)
+            HIP_TRY(ds, t.flags.reserve(g.flag_bytes), "hipHostMalloc flags");
         if (ds->eager)
-            HIP_TRY(ds, hipHostMalloc(reinterpret_cast<void**>(&ds->h_tiles[level]),
-                                      g.tile_bytes, hipHostMallocDefault),
-                    "hipHostMalloc tile copy");
-        ds->tiling[level] = { tile_rows, tile_cols };
+            HIP_TRY(ds, lv.h_tiles.reserve(g.tile_bytes), "hipHostMalloc tile copy");
+        lv.tile_rows = tile_rows;
+        lv.tile_cols = tile_cols;
         return AQZ_OK;
     } catch (...) {
         return ABI_GUARD_FAIL(ds);
@@ -1544,8 +1471,8 @@ aqz_ds_set_input_transpose(aqz_ds* ds, int transpose)
             return rc;
         if (transpose && !ds->d_tin) {
             HIP_TRY(ds, hipStreamSynchronize(ds->stream), "hipStreamSynchronize");
-            HIP_TRY(ds, hipMalloc(&ds->d_tin, ds->bytes[0]), "hipMalloc transposed input");
-            ds->device_bytes += ds->bytes[0];
+            HIP_TRY(ds, ds->d_tin.reserve(ds->lv[0].bytes), "hipMalloc transposed input");
+            ds->device_bytes += ds->lv[0].bytes;
         }
         ds->transpose = transpose != 0;
         ds->last_input = nullptr;
@@ -1577,8 +1504,8 @@ aqz_ds_take_input_frame(aqz_ds* ds,
         if (!ds->last_input)
             return AQZ_OK;
         const bool tiled = tile_rows != 0;
-        const TileGeom g = tiled ? tile_geom(ds, 0, tile_rows, tile_cols)
-                                 : TileGeom{ 1, ds->bytes[0], 0 };
+        const TileGeom g = tiled ? tile_geom(ds, ds->lv[0], tile_rows, tile_cols)
+                                 : TileGeom{ 1, ds->lv[0].bytes, 0 };
         *has_frame = 1;
         if (nbytes)
             *nbytes = g.tile_bytes;
@@ -1589,7 +1516,7 @@ aqz_ds_take_input_frame(aqz_ds* ds,
         if (int rc = bind_device(ds))
             return rc;
         if (tiled) {
-            if (int rc = tile_to_host(ds, ds->last_input, ds->lv[0], tile_rows, tile_cols, g,
+            if (int rc = tile_to_host(ds, ds->last_input, ds->lv[0].desc, tile_rows, tile_cols, g,
                                       dst, tile_nonzero))
                 return rc;
         } else {
@@ -1760,99 +1687,70 @@ aqz_ds_run_device_batch(aqz_ds* ds,
         bool pure_xy = ds->n > 1;
         bool pure_xyz = ds->n > 1;
         for (uint32_t l = 1; l < ds->n; ++l) {
-            pure_xy = pure_xy && ds->xy[l] && !ds->zh[l];
+            const Level& lv = ds->lv[l];
+            pure_xy = pure_xy && lv.xy && !lv.zh;
             // every level halves XY and Z, no odd stack (no pass-through plane)
             // and no stored earlier plane: planes pair up consecutively
-            pure_xyz = pure_xyz && ds->xy[l] && ds->zh[l] &&
-                       ds->lv[l - 1].planes % 2 == 0 && !ds->has_partial[l];
+            pure_xyz = pure_xyz && lv.xy && lv.zh && ds->lv[l - 1].desc.planes % 2 == 0 &&
+                       !lv.has_partial;
         }
         pure_xyz = pure_xyz && n_frames > 0 && (n_frames % (1u << (ds->n - 1))) == 0;
 
-        // Plan runs of up to `maxk` levels per launch.  A 2-D batch always stays
-        // batched: a run the fused cascade cannot take (width or alignment) runs
-        // as one batched single-level generic launch per level.  A volume batch
-        // is all-or-nothing (its fallback is the per-frame state machine).
-        struct Run
-        {
-            uint32_t L, k;
-            bool fused;
-        };
-        auto plan_runs = [&](uint32_t maxk, bool volume) {
-            std::vector<Run> runs;
+        // Runs of up to `maxk` levels per launch, each level into the caller's
+        // buffer.  A 2-D batch always stays batched: a run the fused cascade
+        // cannot take (width or alignment) runs as one batched single-level
+        // generic launch per level (launch_xy_run).  A volume batch is
+        // all-or-nothing (its fallback is the per-frame state machine).
+        const auto out_of = [&](uint32_t l) { return device_out_levels[l]; };
+        const auto volume_takes_every_run = [&] {
             const void* src = device_frames;
-            for (uint32_t L = 1; L < ds->n;) {
-                const uint32_t k = std::min<uint32_t>(ds->n - L, maxk);
+            for (uint32_t L = 1, k; L < ds->n; L += k) {
+                k = std::min<uint32_t>(ds->n - L, aqz::kMaxVolumeLevels);
                 aqz::LevelOut o[aqz::kMaxFusedLevels];
-                for (uint32_t j = 0; j < k; ++j)
-                    o[j] = { device_out_levels[L + j], elems(ds, L + j),
-                             ds->lv[L + j].width, ds->lv[L + j].height };
-                const aqz_level_desc& a = ds->lv[L - 1];
-                const bool ok =
-                  volume ? aqz::volume_supported(ds->dtype, src, a.width, a.height, o, int(k))
-                         : aqz::cascade_supported(ds->dtype, src, elems(ds, L - 1), a.width,
-                                                  a.height, o, int(k));
-                if (!ok && volume)
-                    return std::vector<Run>{};
-                runs.push_back({ L, k, ok });
+                fill_outs(ds, L, k, out_of, o);
+                const aqz_level_desc& a = ds->lv[L - 1].desc;
+                if (!aqz::volume_supported(ds->dtype, src, a.width, a.height, o, int(k)))
+                    return false;
                 src = o[k - 1].ptr;
-                L += k;
             }
-            return runs;
+            return true;
         };
+        const bool batched_2d = pure_xy && n_frames > 0;
+        const bool volume = !batched_2d && pure_xyz && volume_takes_every_run();
 
-        std::vector<Run> runs;
-        bool volume = false;
-        if (pure_xy && n_frames > 0) {
-            runs = plan_runs(aqz::kMaxFusedLevels, false);
-        } else if (pure_xyz) {
-            runs = plan_runs(aqz::kMaxVolumeLevels, true);
-            volume = true;
-        }
-
-        if (!runs.empty()) {
+        if (batched_2d || volume) {
             // Whole batch in batched launches; every frame / plane group independent.
+            const uint32_t maxk = volume ? aqz::kMaxVolumeLevels : aqz::kMaxFusedLevels;
             const void* src = device_frames;
             uint32_t planes = n_frames;
             bool all_fused = true;
-            for (const Run& run : runs) {
+            for (uint32_t L = 1, k; L < ds->n; L += k) {
+                k = std::min<uint32_t>(ds->n - L, maxk);
                 aqz::LevelOut o[aqz::kMaxFusedLevels];
-                for (uint32_t j = 0; j < run.k; ++j)
-                    o[j] = { device_out_levels[run.L + j], elems(ds, run.L + j),
-                             ds->lv[run.L + j].width, ds->lv[run.L + j].height };
-                const aqz_level_desc& a = ds->lv[run.L - 1];
-                hipError_t e = hipSuccess;
+                fill_outs(ds, L, k, out_of, o);
+                hipError_t e;
                 if (volume) {
-                    e = aqz::launch_volume(ds->dtype, ds->method, src, elems(ds, run.L - 1),
-                                           a.width, a.height, o, int(run.k), planes, ds->stream);
-                } else if (run.fused) {
-                    e = aqz::launch_cascade(ds->dtype, ds->method, src, elems(ds, run.L - 1),
-                                            a.width, a.height, o, int(run.k), n_frames,
-                                            ds->stream);
+                    const Level& a = ds->lv[L - 1];
+                    e = aqz::launch_volume(ds->dtype, ds->method, src, a.elems(), a.desc.width,
+                                           a.desc.height, o, int(k), planes, ds->stream);
+                    planes >>= k;
                 } else {
-                    all_fused = false;
-                    const void* s = src;
-                    for (uint32_t j = 0; j < run.k && e == hipSuccess; ++j) {
-                        const aqz_level_desc& in = ds->lv[run.L + j - 1];
-                        e = aqz::launch_xy_generic(ds->dtype, ds->method, s,
-                                                   elems(ds, run.L + j - 1), in.width, in.height,
-                                                   o[j], n_frames, ds->stream);
-                        s = o[j].ptr;
-                    }
+                    bool fused;
+                    e = launch_xy_run(ds, src, L, k, o, n_frames, ds->stream, &fused);
+                    all_fused = all_fused && fused;
                 }
                 if (e != hipSuccess) {
                     rc = ds->fail(e, volume ? "batch volume" : "batch cascade");
                     break;
                 }
-                src = o[run.k - 1].ptr;
-                if (volume)
-                    planes >>= run.k;
+                src = o[k - 1].ptr;
             }
             // a failed launch leaves the counts (and the odd-stack state they
             // carry) where they were
             if (rc == AQZ_OK) {
                 for (uint32_t l = 0; l < ds->n; ++l) {
                     emitted[l] = volume ? (n_frames >> l) : n_frames;
-                    ds->count[l] += emitted[l];
+                    ds->lv[l].count += emitted[l];
                 }
             }
             ds->last_batch_kind = volume ? 2 : (all_fused ? 1 : 3);
@@ -1866,7 +1764,7 @@ aqz_ds_run_device_batch(aqz_ds* ds,
             sink.emitted = &emitted;
             const uint8_t* base = static_cast<const uint8_t*>(device_frames);
             for (uint32_t i = 0; i < n_frames && rc == AQZ_OK; ++i)
-                rc = process_frame(ds, base + size_t(i) * ds->bytes[0], sink);
+                rc = process_frame(ds, base + size_t(i) * ds->lv[0].bytes, sink);
             emitted[0] = n_frames;
         }
         if (out_counts)
@@ -1888,29 +1786,24 @@ stage_lattice(aqz_ds* ds, const aqz_chunk_lattice* lat, uint32_t n_frames, hipSt
               std::vector<const uint64_t*>* dev, int* half_out)
 {
     const size_t need = size_t(ds->n) * n_frames;
-    if (ds->lattice_half < need) {
-        for (hipEvent_t e : ds->lattice_done)
+    if (ds->d_lattice.capacity() < 2 * need * 8 || ds->h_lattice.capacity() < 2 * need * 8) {
+        for (const aqz::Event& e : ds->lattice_done)
             if (e)
                 HIP_TRY(ds, hipEventSynchronize(e), "hipEventSynchronize lattice");
-        (void)hipFree(ds->d_lattice);
-        (void)hipHostFree(ds->h_lattice);
-        ds->d_lattice = nullptr;
-        ds->h_lattice = nullptr;
-        ds->lattice_half = 0;
-        HIP_TRY(ds, hipMalloc(reinterpret_cast<void**>(&ds->d_lattice), 2 * need * 8),
-                "hipMalloc lattice");
-        HIP_TRY(ds, hipHostMalloc(reinterpret_cast<void**>(&ds->h_lattice), 2 * need * 8),
-                "hipHostMalloc lattice");
-        ds->lattice_half = need;
-        for (hipEvent_t& e : ds->lattice_done)
-            if (!e)
-                HIP_TRY(ds, hipEventCreateWithFlags(&e, hipEventDisableTiming), "event");
+        // both go, so the two always have one size (a half is capacity / 2)
+        ds->d_lattice.reset();
+        ds->h_lattice.reset();
+        HIP_TRY(ds, ds->d_lattice.reserve(2 * need * 8), "hipMalloc lattice");
+        HIP_TRY(ds, ds->h_lattice.reserve(2 * need * 8), "hipHostMalloc lattice");
+        for (aqz::Event& e : ds->lattice_done)
+            HIP_TRY(ds, e.create(), "event");
     }
     const int half = int(ds->lattice_calls++ & 1);
     // the batch two calls back read this half: it must have finished
     HIP_TRY(ds, hipEventSynchronize(ds->lattice_done[half]), "hipEventSynchronize lattice");
-    uint64_t* h = ds->h_lattice + size_t(half) * ds->lattice_half;
-    uint64_t* d = ds->d_lattice + size_t(half) * ds->lattice_half;
+    const size_t lattice_half = ds->d_lattice.capacity() / 16; // entries per half
+    uint64_t* h = static_cast<uint64_t*>(ds->h_lattice.get()) + size_t(half) * lattice_half;
+    uint64_t* d = static_cast<uint64_t*>(ds->d_lattice.get()) + size_t(half) * lattice_half;
     dev->assign(ds->n, nullptr);
     for (uint32_t l = 1; l < ds->n; ++l)
         for (uint32_t k = 0; k < n_frames; ++k)
@@ -1949,7 +1842,7 @@ run_tiled(aqz_ds* ds,
     if (ds->n < 2)
         return ds->fail_arg(w + ": the pyramid has no level to tile");
     for (uint32_t l = 1; l < ds->n; ++l) {
-        if (!ds->xy[l] || ds->zh[l])
+        if (!ds->lv[l].xy || ds->lv[l].zh)
             return ds->fail_arg(w + ": pure-XY (2-D) pyramids only; level " + std::to_string(l) +
                                 " does not halve XY alone");
         const uint32_t tr = lat ? lat[l].tile_rows : tile_rows[l];
@@ -1962,8 +1855,8 @@ run_tiled(aqz_ds* ds,
             // every tile of every frame inside the lattice buffer: a bad
             // offset must be an argument error here, not a device fault
             const aqz_chunk_lattice& c = lat[l];
-            const uint64_t ntiles = uint64_t((ds->lv[l].width + tc - 1) / tc) *
-                                    ((ds->lv[l].height + tr - 1) / tr);
+            const uint64_t ntiles = uint64_t((ds->lv[l].desc.width + tc - 1) / tc) *
+                                    ((ds->lv[l].desc.height + tr - 1) / tr);
             const uint64_t tile_bytes = uint64_t(tr) * tc * ds->bpp;
             if (!c.frame_offset_bytes || c.chunk_stride_bytes % ds->bpp ||
                 c.chunk_stride_bytes < tile_bytes)
@@ -2017,7 +1910,7 @@ run_tiled(aqz_ds* ds,
         if (ds->chain_done)
             HIP_TRY(ds, hipStreamWaitEvent(stream, ds->chain_done, 0), "hipStreamWaitEvent chain");
         else
-            HIP_TRY(ds, hipEventCreateWithFlags(&ds->chain_done, hipEventDisableTiming), "event");
+            HIP_TRY(ds, ds->chain_done.create(), "event");
     }
     struct ChainGuard
     {
@@ -2031,14 +1924,10 @@ run_tiled(aqz_ds* ds,
         }
     } chain_guard{ ds, stream, chained };
     if (chained) {
-        const size_t chain_half = size_t(n_frames) * ds->bytes[first_feed];
-        if (ds->d_chain_bytes < 2 * chain_half) {
+        const size_t chain_half = size_t(n_frames) * ds->lv[first_feed].bytes;
+        if (ds->d_chain.capacity() < 2 * chain_half) {
             HIP_TRY(ds, hipStreamSynchronize(stream), "hipStreamSynchronize");
-            (void)hipFree(ds->d_chain);
-            ds->d_chain = nullptr;
-            ds->d_chain_bytes = 0;
-            HIP_TRY(ds, hipMalloc(&ds->d_chain, 2 * chain_half), "hipMalloc chain");
-            ds->d_chain_bytes = 2 * chain_half;
+            HIP_TRY(ds, ds->d_chain.reserve(2 * chain_half), "hipMalloc chain");
         }
     }
     const void* src = device_frames;
@@ -2047,9 +1936,10 @@ run_tiled(aqz_ds* ds,
         const bool feeds = L + k < ds->n;
         aqz::LevelOut o[aqz::kMaxFusedLevels];
         aqz::TiledOut t[aqz::kMaxFusedLevels];
+        // row-major only where the run feeds the next one (below)
+        fill_outs(ds, L, k, [](uint32_t) { return nullptr; }, o);
         for (uint32_t j = 0; j < k; ++j) {
             const uint32_t l = L + j;
-            o[j] = { nullptr, elems(ds, l), ds->lv[l].width, ds->lv[l].height };
             uint8_t* nz = device_tile_nonzero ? device_tile_nonzero[l] : nullptr;
             if (lat)
                 t[j] = { lat[l].device_base, lat[l].tile_rows, lat[l].tile_cols, nz, d_off[l],
@@ -2057,18 +1947,17 @@ run_tiled(aqz_ds* ds,
             else
                 t[j] = { device_out_levels[l], tile_rows[l], tile_cols[l], nz };
         }
-        void* chain = static_cast<uint8_t*>(ds->d_chain) + (run & 1) * (ds->d_chain_bytes / 2);
+        void* chain = ds->d_chain.bytes() + (run & 1) * (ds->d_chain.capacity() / 2);
         if (feeds)
             o[k - 1].ptr = chain;
-        const aqz_level_desc& a = ds->lv[L - 1];
-        if (!aqz::cascade_supported(ds->dtype, src, elems(ds, L - 1), a.width, a.height, o,
-                                    int(k)))
+        const aqz_level_desc& a = ds->lv[L - 1].desc;
+        const uint64_t a_elems = ds->lv[L - 1].elems();
+        if (!aqz::cascade_supported(ds->dtype, src, a_elems, a.width, a.height, o, int(k)))
             return ds->fail_arg(w + ": level " + std::to_string(L - 1) +
                                 " is narrower than one vector load (" + std::to_string(a.width) +
                                 " px)");
-        const hipError_t e = aqz::launch_cascade_tiled(ds->dtype, ds->method, src,
-                                                       elems(ds, L - 1), a.width, a.height, o, t,
-                                                       int(k), n_frames, stream);
+        const hipError_t e = aqz::launch_cascade_tiled(ds->dtype, ds->method, src, a_elems, a.width,
+                                                       a.height, o, t, int(k), n_frames, stream);
         if (e != hipSuccess)
             return e == hipErrorInvalidValue ? ds->fail_arg(w + ": unsupported geometry")
                                              : ds->fail(e, "batch tiled cascade");
@@ -2076,7 +1965,7 @@ run_tiled(aqz_ds* ds,
         L += k;
     }
     for (uint32_t l = 0; l < ds->n; ++l) {
-        ds->count[l] += n_frames;
+        ds->lv[l].count += n_frames;
         if (out_counts)
             out_counts[l] = n_frames;
     }
@@ -2139,7 +2028,7 @@ aqz_ds_tiled_flag_slots(const aqz_ds* ds, uint32_t level, uint32_t tile_rows, ui
     // the fused run holding `level`: levels 1-4, 5-8, ... (kMaxFusedLevels)
     const uint32_t start = 1 + ((level - 1) / aqz::kMaxFusedLevels) * aqz::kMaxFusedLevels;
     const uint32_t k = std::min<uint32_t>(ds->n - start, aqz::kMaxFusedLevels);
-    const uint32_t s = aqz::cascade_tiled_slots(ds->dtype, ds->lv[start - 1].width, int(k),
+    const uint32_t s = aqz::cascade_tiled_slots(ds->dtype, ds->lv[start - 1].desc.width, int(k),
                                                 int(level - start + 1), tile_rows, tile_cols,
                                                 nullptr);
     return s ? s : 1;
@@ -2153,10 +2042,10 @@ namespace {
 uint32_t
 pipe_group(const aqz_ds* ds, uint32_t n_frames)
 {
-    uint32_t g = uint32_t(std::max<size_t>(1, (size_t(64) << 20) / ds->bytes[0]));
+    uint32_t g = uint32_t(std::max<size_t>(1, (size_t(64) << 20) / ds->lv[0].bytes));
     uint32_t align = 1;
     for (uint32_t l = 1; l < ds->n; ++l)
-        if (ds->zh[l])
+        if (ds->lv[l].zh)
             align <<= 1;
     g = std::max(align, (g / align) * align);
     return std::min(g, std::max(align, n_frames));
@@ -2168,30 +2057,32 @@ ensure_pipe(aqz_ds* ds, uint32_t group)
     auto& p = ds->pipe;
     if (p.group >= group)
         return AQZ_OK;
+    // the buffers hold `group` frames only once every one of them is there:
+    // a failed growth is followed by a fresh attempt
+    p.group = 0;
     for (int b = 0; b < 2; ++b) {
-        (void)hipFree(p.d_in[b]);
-        p.d_in[b] = nullptr;
-        for (void* q : p.d_out[b])
-            (void)hipFree(q);
-        p.d_out[b].assign(ds->n, nullptr);
+        // all of the old buffers go before any new one is made
+        p.d_in[b].reset();
+        p.d_out[b].clear();
+        p.d_out[b].resize(ds->n);
     }
     if (!p.s_in) {
-        HIP_TRY(ds, hipStreamCreateWithFlags(&p.s_in, hipStreamNonBlocking), "stream");
-        HIP_TRY(ds, hipStreamCreateWithFlags(&p.s_work, hipStreamNonBlocking), "stream");
-        HIP_TRY(ds, hipStreamCreateWithFlags(&p.s_out, hipStreamNonBlocking), "stream");
+        HIP_TRY(ds, p.s_in.create(), "stream");
+        HIP_TRY(ds, p.s_work.create(), "stream");
+        HIP_TRY(ds, p.s_out.create(), "stream");
         for (int b = 0; b < 2; ++b) {
-            HIP_TRY(ds, hipEventCreateWithFlags(&p.in_done[b], hipEventDisableTiming), "event");
-            HIP_TRY(ds, hipEventCreateWithFlags(&p.work_done[b], hipEventDisableTiming), "event");
-            HIP_TRY(ds, hipEventCreateWithFlags(&p.out_done[b], hipEventDisableTiming), "event");
+            HIP_TRY(ds, p.in_done[b].create(), "event");
+            HIP_TRY(ds, p.work_done[b].create(), "event");
+            HIP_TRY(ds, p.out_done[b].create(), "event");
             // start "done" so the first waits pass
             HIP_TRY(ds, hipEventRecord(p.work_done[b], p.s_work), "event");
             HIP_TRY(ds, hipEventRecord(p.out_done[b], p.s_out), "event");
         }
     }
     for (int b = 0; b < 2; ++b) {
-        HIP_TRY(ds, hipMalloc(&p.d_in[b], size_t(group) * ds->bytes[0]), "hipMalloc pipe");
+        HIP_TRY(ds, p.d_in[b].reserve(size_t(group) * ds->lv[0].bytes), "hipMalloc pipe");
         for (uint32_t l = 1; l < ds->n; ++l)
-            HIP_TRY(ds, hipMalloc(&p.d_out[b][l], size_t(group) * ds->bytes[l]),
+            HIP_TRY(ds, p.d_out[b][l].reserve(size_t(group) * ds->lv[l].bytes),
                     "hipMalloc pipe");
     }
     p.group = group;
@@ -2252,8 +2143,8 @@ aqz_ds_run_host_batch(aqz_ds* ds,
             // upload: buffer b is free once group k-2's kernels are done with it
             HIP_TRY_DRAIN(ds, hipStreamWaitEvent(p.s_in, p.work_done[b], 0), "wait");
             HIP_TRY_DRAIN(ds,
-                    hipMemcpyAsync(p.d_in[b], src + size_t(f0) * ds->bytes[0],
-                                   size_t(g) * ds->bytes[0], hipMemcpyHostToDevice,
+                    hipMemcpyAsync(p.d_in[b].get(), src + size_t(f0) * ds->lv[0].bytes,
+                                   size_t(g) * ds->lv[0].bytes, hipMemcpyHostToDevice,
                                    p.s_in),
                     "hipMemcpyAsync H2D");
             HIP_TRY_DRAIN(ds, hipEventRecord(p.in_done[b], p.s_in), "event");
@@ -2261,8 +2152,11 @@ aqz_ds_run_host_batch(aqz_ds* ds,
             HIP_TRY_DRAIN(ds, hipStreamWaitEvent(p.s_work, p.in_done[b], 0), "wait");
             HIP_TRY_DRAIN(ds, hipStreamWaitEvent(p.s_work, p.out_done[b], 0), "wait");
             std::vector<uint32_t> counts(ds->n, 0);
-            rc = aqz_ds_run_device_batch(ds, p.d_in[b], g, p.d_out[b].data(),
-                                         counts.data(), p.s_work);
+            std::vector<void*> d_out(ds->n);
+            for (uint32_t l = 1; l < ds->n; ++l)
+                d_out[l] = p.d_out[b][l].get();
+            rc = aqz_ds_run_device_batch(ds, p.d_in[b].get(), g, d_out.data(), counts.data(),
+                                         p.s_work);
             if (rc)
                 return drain(rc);
             HIP_TRY_DRAIN(ds, hipEventRecord(p.work_done[b], p.s_work), "event");
@@ -2272,9 +2166,9 @@ aqz_ds_run_host_batch(aqz_ds* ds,
                 if (!counts[l])
                     continue;
                 uint8_t* dst = static_cast<uint8_t*>(host_out_levels[l]) +
-                               size_t(total[l]) * ds->bytes[l];
+                               size_t(total[l]) * ds->lv[l].bytes;
                 HIP_TRY_DRAIN(ds,
-                        hipMemcpyAsync(dst, p.d_out[b][l], size_t(counts[l]) * ds->bytes[l],
+                        hipMemcpyAsync(dst, d_out[l], size_t(counts[l]) * ds->lv[l].bytes,
                                        hipMemcpyDeviceToHost, p.s_out),
                         "hipMemcpyAsync D2H");
                 total[l] += counts[l];
@@ -2307,7 +2201,7 @@ aqz_ds_stream_tiled_runs(const aqz_ds* ds)
 size_t
 aqz_ds_level_bytes(const aqz_ds* ds, uint32_t level)
 {
-    return (ds && level < ds->n) ? ds->bytes[level] : 0;
+    return (ds && level < ds->n) ? ds->lv[level].bytes : 0;
 }
 
 uint32_t
