@@ -43,6 +43,7 @@ EXPORTS = (
     "aqz_blosc_filter_device", "aqz_crc32c_device", "aqz_tile_slices",
     "aqz_tile_frame_device_sliced",
     "aqz_ds_run_device_batch_chunked", "aqz_chunk_frame_offsets",
+    "aqz_ds_run_device_volume_tiled", "aqz_ds_run_device_volume_chunked",
     "aqz_blosc_blocksize", "aqz_blosc_frame_from_filtered", "aqz_blosc_ctx_create",
     "aqz_blosc_ctx_destroy", "aqz_blosc_compress_device", "aqz_blosc_codec_info",
     "aqz_blosc_lz4_frames_device", "aqz_blosc_lz4_compress_device",
@@ -190,6 +191,8 @@ def lib() -> ctypes.CDLL:
                                                 ctypes.POINTER(vp), ctypes.POINTER(u32), vp]
     L.aqz_ds_run_device_batch_chunked.argtypes = [vp, vp, u32, ctypes.POINTER(ChunkLattice),
                                                   ctypes.POINTER(vp), ctypes.POINTER(u32), vp]
+    L.aqz_ds_run_device_volume_tiled.argtypes = L.aqz_ds_run_device_batch_tiled.argtypes
+    L.aqz_ds_run_device_volume_chunked.argtypes = L.aqz_ds_run_device_batch_chunked.argtypes
     L.aqz_chunk_frame_offsets.argtypes = [ctypes.POINTER(Dimension), u32, u32, ctypes.c_uint64,
                                           u32, ctypes.POINTER(ctypes.c_uint64),
                                           ctypes.POINTER(ctypes.c_uint64),
@@ -591,6 +594,47 @@ class Downsampler:
             nz = (ctypes.c_void_p * n)(*[int(p) if p else 0 for p in device_nonzero])
         counts = (ctypes.c_uint32 * n)()
         self._check(lib().aqz_ds_run_device_batch_chunked(
+            self._h, device_frames, n_frames, arr, nz, counts,
+            ctypes.c_void_p(stream) if stream else None))
+        return list(counts)
+
+    def run_device_volume_tiled(self, device_frames: int, n_frames: int, tiles,
+                                device_outs, device_nonzero=None, stream: int = 0):
+        """run_device_batch_tiled for a volume pyramid (every level halves
+        X, Y and Z), from the fused volume kernel: level L emits
+        n_frames >> L planes, tiled as there, with one flag byte per tile
+        per plane in `device_nonzero[L]`.  Returns planes emitted per level."""
+        n = self.n_levels
+        tr = (ctypes.c_uint32 * n)(*[int(t[0]) if t else 0 for t in tiles])
+        tc = (ctypes.c_uint32 * n)(*[int(t[1]) if t else 0 for t in tiles])
+        outs = (ctypes.c_void_p * n)(*[int(p) if p else 0 for p in device_outs])
+        nz = None
+        if device_nonzero is not None:
+            nz = (ctypes.c_void_p * n)(*[int(p) if p else 0 for p in device_nonzero])
+        counts = (ctypes.c_uint32 * n)()
+        self._check(lib().aqz_ds_run_device_volume_tiled(
+            self._h, device_frames, n_frames, tr, tc, outs, nz, counts,
+            ctypes.c_void_p(stream) if stream else None))
+        return list(counts)
+
+    def run_device_volume_chunked(self, device_frames: int, n_frames: int, lattices,
+                                  device_nonzero=None, stream: int = 0):
+        """aqz_ds_run_device_volume_chunked: `lattices[L]` as for
+        run_device_batch_chunked, its frame_offset_bytes list holding
+        n_frames >> L entries (one per plane level L emits)."""
+        n = self.n_levels
+        arr = (ChunkLattice * n)()
+        keep = []
+        for L in range(1, n):
+            base, cap, tr, tc, stride, offs = lattices[L]
+            o = (ctypes.c_uint64 * max(n_frames >> L, 1))(*offs)
+            keep.append(o)
+            arr[L] = ChunkLattice(int(base), cap, tr, tc, stride, o)
+        nz = None
+        if device_nonzero is not None:
+            nz = (ctypes.c_void_p * n)(*[int(p) if p else 0 for p in device_nonzero])
+        counts = (ctypes.c_uint32 * n)()
+        self._check(lib().aqz_ds_run_device_volume_chunked(
             self._h, device_frames, n_frames, arr, nz, counts,
             ctypes.c_void_p(stream) if stream else None))
         return list(counts)

@@ -1,15 +1,16 @@
 // ds_dispatch.cpp — the host entry of every launcher of ds_kernels.hh.
 //
-// launch_cascade, launch_cascade_tiled and launch_volume plan here
+// launch_cascade, launch_cascade_tiled, launch_volume and launch_volume_tiled
+// plan here
 // (ds_plan.hh: the process-wide switches, the device's LDS cap), record the
 // plan's line in the launch log and hand the plan to run_cascade,
-// run_cascade_tiled or run_volume of the dtype's kernel shard; the other
-// launchers are routed as they are.
+// run_cascade_tiled, run_volume or run_volume_tiled of the dtype's kernel
+// shard; the other launchers are routed as they are.
 //
 // ds_kernels.hip is compiled AQZ_SHARDS times (acquire-zarr_amd/Makefile);
 // shard k holds the kernels of the dtypes whose code % AQZ_SHARDS == k and
 // names its launchers <launcher>_shard<k>.  This file is compiled once.  A
-// tools/ probe includes it after ds_kernels.hip, unsharded: the three planned
+// tools/ probe includes it after ds_kernels.hip, unsharded: the planned
 // launchers then call the one set of run_* functions.
 #include "ds_kernels.hh"
 
@@ -51,6 +52,9 @@ AQZ_DECLARE_SHARDS(run_cascade_tiled,
 AQZ_DECLARE_SHARDS(run_volume,
                    (const VolumePlan&, const void*, uint64_t, uint32_t, uint32_t,
                     const LevelOut*, hipStream_t))
+AQZ_DECLARE_SHARDS(run_volume_tiled,
+                   (const VolumeTiledPlan&, const void*, uint64_t, uint32_t, uint32_t,
+                    const LevelOut*, const TiledOut*, hipStream_t))
 #else
 #define AQZ_ROUTE(name, dtype, args) return name args
 #endif
@@ -115,6 +119,20 @@ launch_volume(int dtype, int method, const void* src, uint64_t src_frame_elems, 
     if (launch_log_on())
         launch_log_record("%s", format_plan(pl).c_str());
     AQZ_ROUTE(run_volume, dtype, (pl, src, src_frame_elems, W, H, outs, stream));
+}
+
+hipError_t
+launch_volume_tiled(int dtype, int method, const void* src, uint64_t src_frame_elems, uint32_t W,
+                    uint32_t H, const LevelOut* outs, const TiledOut* touts, int n_out,
+                    uint32_t n_planes, hipStream_t stream)
+{
+    const VolumeTiledPlan pl = plan_volume_tiled(dtype, method, src, src_frame_elems, W, H, outs,
+                                                 touts, n_out, n_planes, launch_switches());
+    if (!pl.valid)
+        return hipErrorInvalidValue;
+    if (launch_log_on())
+        launch_log_record("%s", format_plan(pl).c_str());
+    AQZ_ROUTE(run_volume_tiled, dtype, (pl, src, src_frame_elems, W, H, outs, touts, stream));
 }
 
 #if AQZ_SHARDS > 1

@@ -46,9 +46,21 @@ hipError_t launch_volume(int dtype, int method, const void* src, uint64_t src_fr
                          uint32_t W, uint32_t H, const LevelOut* outs, int n_out,
                          uint32_t n_planes, hipStream_t stream);
 
+// launch_volume with every level written chunk-tiled from registers, plane k
+// of level L as frame k of touts[L-1] (n_planes >> L planes: that many
+// frame_offsets entries for a chunk lattice).  One kernel; its first waves
+// zero-fill the tile overhang; touts[i].nonzero, when set, is cleared by a
+// fill queued first and holds one byte per tile per emitted plane.  outs[i]
+// gives level i's geometry; its ptr, when non-null, also receives the level
+// row-major (the input of a following launch).
+hipError_t launch_volume_tiled(int dtype, int method, const void* src, uint64_t src_frame_elems,
+                               uint32_t W, uint32_t H, const LevelOut* outs,
+                               const TiledOut* touts, int n_out, uint32_t n_planes,
+                               hipStream_t stream);
+
 // One XY level, any width/alignment.
 // (The dtype-dispatching launchers are routed by ds_dispatch.cpp to the build
-// shard of ds_kernels.hip that holds the dtype's kernels; the three above are
+// shard of ds_kernels.hip that holds the dtype's kernels; the four above are
 // planned there first, ds_plan.hh.)
 hipError_t launch_xy_generic(int dtype, int method, const void* src, uint64_t src_frame_elems,
                              uint32_t w, uint32_t h, const LevelOut& out, uint32_t n_frames,

@@ -728,10 +728,12 @@ nonzero_bits(T x)
 // past the level inside the padded pw x ph area are stored as zero — the
 // bytes Chunk::write_tile_rows leaves in an overhanging tile slot
 // (chunk.cpp:17-58) — and positions past the padding are skipped.  `wc0` is
-// the wave's first level-0 column (uniform).  Flags: see CascadeParams.
-template<typename T, int C, int J, int RO, int CO, bool EDGE, int MODE>
+// the wave's first level-0 column (uniform).  Flags: see TiledLevel.  P is
+// the kernel's parameter block (CascadeParams, VolumeTiledParams): it supplies
+// the level sizes w[], h[] and the TiledLevel array tl[].
+template<typename T, int C, int J, int RO, int CO, bool EDGE, int MODE, typename P>
 __device__ __forceinline__ void
-store_level_tiled(const CascadeParams& p,
+store_level_tiled(const P& p,
                   const T (&out)[RO][CO],
                   uint32_t f,
                   uint32_t wc0,
@@ -866,33 +868,45 @@ store_level_tiled(const CascadeParams& p,
 
 // Level I's TiledLevel with compile-time kernarg offsets (indexing p.tl with
 // a runtime I would copy the array to scratch).
+template<typename P>
 __device__ __forceinline__ TiledLevel
-tiled_level(const CascadeParams& p, int I)
+tiled_level(const P& p, int I)
 {
     static_assert(kMaxFusedLevels == 4, "tiled_level");
     return I == 0 ? p.tl[0] : I == 1 ? p.tl[1] : I == 2 ? p.tl[2] : p.tl[3];
 }
 
-template<typename T>
+// NLV > 0: the fused volume's run of NLV levels.  `n_frames` then counts
+// plane groups, level I + 1 emits 2^(NLV-1-I) planes per group, and a group's
+// items are every level's zrows once per such plane (plan_volume_tiled).
+template<typename T, int NLV = 0, typename P>
 __device__ __forceinline__ void
-zero_fill_tiled(const CascadeParams& p, uint32_t z, uint32_t nz, int lane, int n_out,
+zero_fill_tiled(const P& p, uint32_t z, uint32_t nz, int lane, int n_out,
                 uint32_t n_frames)
 {
     constexpr int E = 16 / int(sizeof(T));
     const uint32_t items = p.zitems * n_frames; // < 2^32: checked at launch
     for (uint32_t it = z; it < items; it += nz) {
-        const uint32_t f = p.zdiv.div(it);
+        uint32_t f = p.zdiv.div(it);
         uint32_t rem = it - f * p.zitems;
         int I = 0;
 #pragma unroll
         for (int k = 0; k < kMaxFusedLevels - 1; ++k) {
-            const uint32_t zr = k == 0 ? p.tl[0].zrows : k == 1 ? p.tl[1].zrows : p.tl[2].zrows;
+            uint32_t zr = k == 0 ? p.tl[0].zrows : k == 1 ? p.tl[1].zrows : p.tl[2].zrows;
+            if constexpr (NLV > 0)
+                zr <<= (NLV - 1 - k > 0 ? NLV - 1 - k : 0);
             if (I == k && I + 1 < n_out && rem >= zr) {
                 rem -= zr;
                 ++I;
             }
         }
         const TiledLevel t = tiled_level(p, I);
+        if constexpr (NLV > 0) {
+            // the level's plane within the group, then the row item within it
+            const uint32_t zz = rem / t.zrows;
+            rem -= zz * t.zrows;
+            f = (f << (NLV - 1 - I)) + zz;
+        }
         const uint32_t tr = t.tr, tc = t.tc, pw = t.pw;
         const uint32_t cw = min(t.cov_w, pw), chh = min(t.cov_h, t.ph);
         const uint32_t row = cw < pw ? rem : chh + rem;
@@ -1496,10 +1510,25 @@ struct VolumeParams
     uint32_t h[kMaxVolumeLevels];
 };
 
+// volume_kernel<..., TILED>: every level also (dst[J-1] null: only) goes out in
+// chunk-tile order, plane k of level J as frame k of tl[J-1]; one flag byte
+// per tile, cleared before the launch (TiledLevel::slots == 0).  The grid's
+// first zwaves / (waves per block) blocks zero-fill the tile overhang the
+// units do not reach (zero_fill_tiled<T, NL>).  tl[] has the cascade's length
+// so that both parameter blocks feed the same tiled stores; a run uses its
+// first n_out entries.
+struct VolumeTiledParams : VolumeParams
+{
+    TiledLevel tl[kMaxFusedLevels];
+    uint32_t zitems; // zero-fill items per plane group, all levels
+    FastDiv zdiv;    // by zitems
+    uint32_t zwaves;
+};
+
 template<typename T, int M, int C, int J, int NL, int ZI, int RI, int CI,
-         bool EDGE, bool NTS>
+         bool EDGE, bool NTS, bool TILED = false, typename P = VolumeParams>
 __device__ __forceinline__ void
-volume_level(const VolumeParams& p,
+volume_level(const P& p,
              const T (&in)[ZI][RI][CI],
              uint32_t g,
              uint32_t row0,
@@ -1534,12 +1563,21 @@ volume_level(const VolumeParams& p,
         // level-J frame index: plane group g covers 2^(NL-J) frames there
         T* dst = reinterpret_cast<T*>(p.dst[J - 1]) +
                  (uint64_t(g) * ZO + z) * p.dst_frame_elems[J - 1];
-        store_level<T, C, J, RO, CO, EDGE, NTS>(dst, out[z], p.w[J - 1],
-                                                p.h[J - 1], col0, row0, lane);
+        if constexpr (TILED) {
+            // a row-major copy only where the next launch reads this level
+            if (p.dst[J - 1])
+                store_level<T, C, J, RO, CO, EDGE, NTS>(dst, out[z], p.w[J - 1],
+                                                        p.h[J - 1], col0, row0, lane);
+            store_level_tiled<T, C, J, RO, CO, EDGE, 2>(p, out[z], g * uint32_t(ZO) + z,
+                                                        col0 - uint32_t(lane) * C, row0, lane);
+        } else {
+            store_level<T, C, J, RO, CO, EDGE, NTS>(dst, out[z], p.w[J - 1],
+                                                    p.h[J - 1], col0, row0, lane);
+        }
     }
     if constexpr (J < NL) {
-        volume_level<T, M, C, J + 1, NL, ZO, RO, CO, EDGE, NTS>(p, out, g, row0,
-                                                               col0, lane);
+        volume_level<T, M, C, J + 1, NL, ZO, RO, CO, EDGE, NTS, TILED>(p, out, g, row0,
+                                                                      col0, lane);
     }
 }
 
@@ -1577,9 +1615,10 @@ volume_load(const VolumeParams& p,
     }
 }
 
-template<typename T, int M, int NL, int C, bool EDGE, bool NTL>
+template<typename T, int M, int NL, int C, bool EDGE, bool NTL, bool TILED = false,
+         typename P = VolumeParams>
 __device__ __forceinline__ void
-volume_unit(const VolumeParams& p,
+volume_unit(const P& p,
             uint32_t g,
             uint32_t row0,
             uint32_t col0,
@@ -1588,7 +1627,7 @@ volume_unit(const VolumeParams& p,
     constexpr int R = 1 << NL;
     T v[R][R][C];
     volume_load<T, M, NL, C, EDGE, NTL>(p, g, row0, col0, v);
-    volume_level<T, M, C, 1, NL, R, R, C, EDGE, true>(p, v, g, row0, col0, lane);
+    volume_level<T, M, C, 1, NL, R, R, C, EDGE, true, TILED>(p, v, g, row0, col0, lane);
 }
 
 // Unit u's plane group, first row and this lane's first column; true when
@@ -1626,22 +1665,38 @@ volume_coords(const VolumeParams& p, uint32_t u, int lane, uint32_t& g, uint32_t
 // nontemporal loads and 0.55-0.56 with plain ones; the 0.82 once measured
 // with plain loads came from the Infinity Cache holding the launch's
 // 128 MiB read set between launches.
+//
+// TILED (launch_volume_tiled; one unit per wave, columns first, nontemporal
+// loads): the levels go out in chunk-tile order — VolumeTiledParams.
 template<typename T, int M, int NL, bool NTL, int UPW, int C = 16 / int(sizeof(T)),
-         bool ZFAST = false>
+         bool ZFAST = false, bool TILED = false>
 __global__ __launch_bounds__(256) void
-volume_kernel(VolumeParams p)
+volume_kernel(std::conditional_t<TILED, VolumeTiledParams, VolumeParams> p)
 {
     const int lane = threadIdx.x & 63;
-    const uint32_t w =
-      blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t blk = blockIdx.x;
+    if constexpr (TILED) {
+        static_assert(UPW == 1 && !ZFAST && NTL, "the tiled volume kernel's one form");
+        // The first blocks zero-fill the tile overhang, as in cascade_kernel.
+        const uint32_t wpb = blockDim.x >> 6;
+        const uint32_t zb = p.zwaves / wpb;
+        if (blk < zb) {
+            zero_fill_tiled<T, NL>(p, blk * wpb + wave, p.zwaves, lane, NL,
+                                   p.total_units / (p.units_x * p.units_y));
+            return;
+        }
+        blk -= zb;
+    }
+    const uint32_t w = blk * (blockDim.x >> 6) + wave;
     if constexpr (UPW == 1) {
         if (w >= p.total_units)
             return;
         uint32_t g, row0, col0;
         if (volume_coords<NL, C, ZFAST>(p, w, lane, g, row0, col0))
-            volume_unit<T, M, NL, C, false, NTL>(p, g, row0, col0, lane);
+            volume_unit<T, M, NL, C, false, NTL, TILED>(p, g, row0, col0, lane);
         else
-            volume_unit<T, M, NL, C, true, NTL>(p, g, row0, col0, lane);
+            volume_unit<T, M, NL, C, true, NTL, TILED>(p, g, row0, col0, lane);
     } else {
         constexpr int R = 1 << NL;
         const uint32_t u0 = w * UPW;
@@ -2105,9 +2160,33 @@ fill_frames(P& p, const Plan& pl, const void* src, uint64_t src_frame_elems, uin
     }
 }
 
+// Fill level i's TiledLevel from its plan and output.
+void
+fill_tiled_level(TiledLevel& q, const TiledLevelPlan& l, const TiledOut& t)
+{
+    q.tdst = static_cast<uint8_t*>(t.ptr);
+    q.flags = t.nonzero;
+    q.tframe_elems = l.tframe_elems;
+    q.foff = t.frame_offsets;
+    q.tstride = l.tstride;
+    q.tr = t.tile_rows;
+    q.tc = t.tile_cols;
+    q.ntx = l.ntx;
+    q.pw = l.pw;
+    q.ph = l.ph;
+    q.slots = l.slots;
+    q.slots_x = l.slots_x;
+    q.flags_frame = l.flags_frame;
+    q.cov_w = l.cov_w;
+    q.cov_h = l.cov_h;
+    q.zrows = l.zrows;
+    q.dr = FastDiv::make(t.tile_rows);
+    q.dc = FastDiv::make(t.tile_cols);
+}
+
 } // namespace
 
-// The three planned launchers: the plan (ds_plan.hh) has decided everything;
+// The planned launchers: the plan (ds_plan.hh) has decided everything;
 // these fill the kernel parameters from it and pick the instantiation its
 // selector fields name.  A selector value no kernel is built for is an error,
 // never another kernel.
@@ -2201,25 +2280,7 @@ AQZ_SHARDED(run_cascade_tiled)(const TiledPlan& pl, const void* src, uint64_t sr
     for (int i = 0; i < pl.n_out; ++i) {
         const TiledOut& t = touts[i];
         const TiledLevelPlan& l = pl.lv[i];
-        TiledLevel& q = p.tl[i];
-        q.tdst = static_cast<uint8_t*>(t.ptr);
-        q.flags = t.nonzero;
-        q.tframe_elems = l.tframe_elems;
-        q.foff = t.frame_offsets;
-        q.tstride = l.tstride;
-        q.tr = t.tile_rows;
-        q.tc = t.tile_cols;
-        q.ntx = l.ntx;
-        q.pw = l.pw;
-        q.ph = l.ph;
-        q.slots = l.slots;
-        q.slots_x = l.slots_x;
-        q.flags_frame = l.flags_frame;
-        q.cov_w = l.cov_w;
-        q.cov_h = l.cov_h;
-        q.zrows = l.zrows;
-        q.dr = FastDiv::make(t.tile_rows);
-        q.dc = FastDiv::make(t.tile_cols);
+        fill_tiled_level(p.tl[i], l, t);
         if (l.clear_flags) {
             const hipError_t e =
               hipMemsetAsync(t.nonzero, 0, size_t(pl.n_frames) * l.ntx * l.nty, stream);
@@ -2308,6 +2369,49 @@ AQZ_SHARDED(run_volume)(const VolumePlan& pl, const void* src, uint64_t src_fram
                 return with_flag(pl.ntl, [&](auto ntltag) -> hipError_t {
                     return run(ntltag, int_tag<1>{}, std::false_type{});
                 });
+            };
+            if (pl.n_out == 1)
+                return go(int_tag<1>{});
+            if (pl.n_out == 2)
+                return go(int_tag<2>{});
+            return hipErrorInvalidValue;
+        });
+    });
+}
+
+hipError_t
+AQZ_SHARDED(run_volume_tiled)(const VolumeTiledPlan& pl, const void* src,
+                              uint64_t src_frame_elems, uint32_t W, uint32_t H,
+                              const LevelOut* outs, const TiledOut* touts, hipStream_t stream)
+{
+    if (!pl.valid)
+        return hipErrorInvalidValue;
+    VolumeTiledParams p{};
+    fill_frames(p, pl, src, src_frame_elems, W, H, outs);
+    for (int i = 0; i < pl.n_out; ++i) {
+        fill_tiled_level(p.tl[i], pl.lv[i], touts[i]);
+        if (pl.lv[i].clear_flags) {
+            // level i + 1 emits n_planes >> (i + 1) planes
+            const hipError_t e = hipMemsetAsync(
+              touts[i].nonzero, 0, size_t(pl.n_planes >> (i + 1)) * pl.lv[i].flags_frame, stream);
+            if (e != hipSuccess)
+                return e;
+        }
+    }
+    p.zitems = pl.zitems;
+    p.zdiv = FastDiv::make(pl.zitems ? pl.zitems : 1);
+    p.zwaves = pl.zwaves;
+    const dim3 grid(pl.grid), block(pl.block);
+    return with_dtype(pl.dtype, [&](auto tag) -> hipError_t {
+        using T = decltype(tag);
+        constexpr int CZ = 16 / int(sizeof(T));
+        return with_method(pl.method, [&](auto mtag) -> hipError_t {
+            constexpr int M = decltype(mtag)::value;
+            auto go = [&](auto nltag) -> hipError_t {
+                hipLaunchKernelGGL(
+                  (volume_kernel<T, M, decltype(nltag)::value, true, 1, CZ, false, true>), grid,
+                  block, 0, stream, p);
+                return hipGetLastError();
             };
             if (pl.n_out == 1)
                 return go(int_tag<1>{});

@@ -724,6 +724,104 @@ format_plan(const VolumePlan& p)
                 int(p.ntl), int(p.zfast), p.upw);
 }
 
+VolumeTiledPlan
+plan_volume_tiled(int dtype, int method, const void* src, uint64_t, uint32_t W, uint32_t H,
+                  const LevelOut* outs, const TiledOut* touts, int n_out, uint32_t n_planes,
+                  const LaunchSwitches& sw)
+{
+    VolumeTiledPlan p;
+    if (!volume_supported(dtype, src, W, H, outs, n_out) || n_planes == 0 ||
+        n_planes % (1u << n_out) != 0 || !method_valid(method) || !touts)
+        return p;
+    const size_t b = dtype_bytes(dtype);
+    p.dtype = dtype;
+    p.method = method;
+    p.n_out = n_out;
+    p.bytes = uint32_t(b);
+    p.n_planes = n_planes;
+    // plan_volume's units, one per wave, columns first
+    const uint32_t C = 16 / p.bytes;
+    const uint32_t R = 1u << n_out;
+    const uint32_t groups = n_planes >> n_out;
+    p.units_x = (W + 64 * C - 1) / (64 * C);
+    p.units_y = (H + R - 1) / R;
+    const uint64_t total = uint64_t(p.units_x) * p.units_y * groups;
+    if (total >= (1ull << 31))
+        return p;
+    p.total_units = uint32_t(total);
+    uint64_t zitems = 0, zbytes = 0;
+    for (int i = 0; i < n_out; ++i) {
+        const TiledOut& t = touts[i];
+        if (!t.ptr || t.tile_rows == 0 || t.tile_cols == 0 ||
+            reinterpret_cast<uintptr_t>(t.ptr) % b != 0)
+            return p;
+        TiledLevelPlan& q = p.lv[i];
+        q.ntx = (outs[i].w + t.tile_cols - 1) / t.tile_cols;
+        q.nty = (outs[i].h + t.tile_rows - 1) / t.tile_rows;
+        const uint64_t pw = uint64_t(q.ntx) * t.tile_cols, ph = uint64_t(q.nty) * t.tile_rows;
+        if (pw >= (1ull << 31) || ph >= (1ull << 31))
+            return p;
+        q.tframe_elems = pw * ph;
+        q.tstride = t.frame_offsets ? t.tile_stride : uint64_t(t.tile_rows) * t.tile_cols;
+        if (q.tstride < uint64_t(t.tile_rows) * t.tile_cols)
+            return p;
+        q.pw = uint32_t(pw);
+        q.ph = uint32_t(ph);
+        // what the units reach at this level, as in plan_cascade_tiled; the
+        // zero-fill waves take the rest of the padded area: columns past
+        // cov_w of every padded row, else the rows past cov_h
+        q.cov_w = p.units_x * ((64u * C) >> (i + 1));
+        q.cov_h = p.units_y * (R >> (i + 1));
+        q.zrows = q.cov_w < pw ? uint32_t(ph) : (q.cov_h < ph ? uint32_t(ph) - q.cov_h : 0u);
+        // one flag byte per tile, cleared ahead of the kernel (no nested slots)
+        q.slots = 0;
+        q.slots_x = 1;
+        q.flags_frame = q.ntx * q.nty;
+        q.clear_flags = t.nonzero != nullptr;
+        const uint32_t per_group = 1u << (n_out - 1 - i); // the level's planes per group
+        zitems += uint64_t(q.zrows) * per_group;
+        const uint64_t cw = std::min(q.cov_w, q.pw), chh = std::min(q.cov_h, q.ph);
+        zbytes += (uint64_t(q.pw) * q.ph - cw * chh) * b * per_group;
+    }
+    if (zitems * groups >= (1ull << 32))
+        return p;
+    p.zitems = uint32_t(zitems);
+    // zero-fill waves by plan_cascade_tiled's rule: one per 128 KiB of
+    // overhang, at most 32 overhang rows per wave for 1-byte types, 64..4096
+    zbytes *= groups;
+    const int zi = sw.tiled_zrows_per_wave >= 0 ? sw.tiled_zrows_per_wave : (b == 1 ? 32 : 0);
+    uint64_t zw = (zbytes >> 17) + 1;
+    if (zi > 0)
+        zw = std::max<uint64_t>(zw, (zitems * groups + zi - 1) / uint64_t(zi));
+    p.zwaves = zitems ? uint32_t(std::min<uint64_t>(std::max<uint64_t>(zw, 64), 4096)) : 0u;
+    p.wpb = 4;
+    p.block = 64 * p.wpb;
+    p.main_blocks = grid_for(total, p.wpb, 0);
+    // zero-fill blocks: a whole number of 8-block (one per XCD) groups
+    const uint32_t zblocks = ((p.zwaves + p.wpb - 1) / p.wpb + 7) & ~7u;
+    p.zwaves = zblocks * p.wpb;
+    p.grid = zblocks + p.main_blocks;
+    p.valid = true;
+    return p;
+}
+
+std::string
+format_plan(const VolumeTiledPlan& p)
+{
+    std::string s = line("family=volume_tiled dtype=%u method=%d n_out=%d grid=%u block=%u "
+                         "units=%u units_x=%u units_y=%u wpb=%u zwaves=%u zitems=%u "
+                         "main_blocks=%u",
+                         p.bytes, p.method, p.n_out, p.grid, p.block, p.total_units, p.units_x,
+                         p.units_y, p.wpb, p.zwaves, p.zitems, p.main_blocks);
+    for (int i = 0; i < p.n_out; ++i) {
+        const TiledLevelPlan& q = p.lv[i];
+        s += line(" ntx%d=%u nty%d=%u pw%d=%u ph%d=%u cov_w%d=%u cov_h%d=%u zrows%d=%u", i + 1,
+                  q.ntx, i + 1, q.nty, i + 1, q.pw, i + 1, q.ph, i + 1, q.cov_w, i + 1, q.cov_h,
+                  i + 1, q.zrows);
+    }
+    return s.substr(0, 319); // the launch log's line length
+}
+
 uint32_t
 tile_slices(uint32_t tile_rows, uint32_t tile_cols)
 {

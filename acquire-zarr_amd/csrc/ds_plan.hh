@@ -1,5 +1,5 @@
-// ds_plan.hh — what launch_cascade, launch_cascade_tiled and launch_volume
-// launch: host-only integer arithmetic over the dtype size, method, geometry,
+// ds_plan.hh — what launch_cascade, launch_cascade_tiled, launch_volume and
+// launch_volume_tiled launch: host-only integer arithmetic over the dtype size, method, geometry,
 // buffer alignment and the $AQZ_* A/B switches.  No HIP type appears here
 // (ds_plan.cpp builds with a plain C++ compiler; tests/cpp/plan_probe.cpp
 // runs it on the CPU).  ds_dispatch.cpp builds a plan per launch, logs
@@ -237,6 +237,25 @@ struct VolumePlan
     uint32_t units_x = 0, units_y = 0, total_units = 0;
 };
 
+// launch_volume_tiled: VolumePlan's unit geometry (one unit per wave, columns
+// first, nontemporal loads) with one TiledLevelPlan per level of the run.
+// Level i + 1 emits n_planes >> (i + 1) planes; lv[i].zrows counts the
+// zero-fill items of one such plane, zitems those of one plane group (every
+// level's zrows times its 2^(n_out-1-i) planes per group).  Flags are one
+// cleared byte per tile (clear_flags where the level has a flag buffer).
+struct VolumeTiledPlan
+{
+    bool valid = false;
+    int dtype = 0, method = 0, n_out = 0;
+    uint32_t bytes = 0;
+    // selectors: volume_kernel<T, M, n_out, true, 1, 16 / bytes, false, true>
+    uint32_t grid = 0, block = 256, wpb = 4;
+    uint32_t n_planes = 0;
+    uint32_t units_x = 0, units_y = 0, total_units = 0;
+    uint32_t zitems = 0, zwaves = 0, main_blocks = 0;
+    TiledLevelPlan lv[kMaxVolumeLevels];
+};
+
 // `lds_cap`: the device's LDS per workgroup, less the band kernel's static
 // arrival counter (ds_dispatch.cpp asks the device once).
 CascadePlan plan_cascade(int dtype, int method, const void* src, uint64_t src_frame_elems,
@@ -248,11 +267,20 @@ TiledPlan plan_cascade_tiled(int dtype, int method, const void* src, uint64_t sr
 VolumePlan plan_volume(int dtype, int method, const void* src, uint64_t src_frame_elems,
                        uint32_t W, uint32_t H, const LevelOut* outs, int n_out,
                        uint32_t n_planes, const LaunchSwitches& sw);
+// touts[i].frame_offsets, when set, holds n_planes >> (i + 1) entries.
+// Invalid on top of plan_volume's rules: a null, misaligned or zero-shaped
+// tile output, a tile stride below one tile, a padded side or the unit count
+// at 2^31 or more, zero-fill items at 2^32 or more.
+VolumeTiledPlan plan_volume_tiled(int dtype, int method, const void* src,
+                                  uint64_t src_frame_elems, uint32_t W, uint32_t H,
+                                  const LevelOut* outs, const TiledOut* touts, int n_out,
+                                  uint32_t n_planes, const LaunchSwitches& sw);
 
 // The launch log's line (launch_log.hh) for a valid plan: family=cascade or
-// family=band, family=tiled, family=volume.
+// family=band, family=tiled, family=volume, family=volume_tiled.
 std::string format_plan(const CascadePlan& p);
 std::string format_plan(const TiledPlan& p);
 std::string format_plan(const VolumePlan& p);
+std::string format_plan(const VolumeTiledPlan& p);
 
 } // namespace aqz

@@ -1781,9 +1781,11 @@ namespace {
 
 // Per-level frame offsets of a chunk-lattice batch into the device (elements),
 // through one half of the pinned staging; returns the device pointers.
+// `halving`: level l carries n_frames >> l offsets (a volume batch), not
+// n_frames.
 int
 stage_lattice(aqz_ds* ds, const aqz_chunk_lattice* lat, uint32_t n_frames, hipStream_t stream,
-              std::vector<const uint64_t*>* dev, int* half_out)
+              std::vector<const uint64_t*>* dev, int* half_out, bool halving = false)
 {
     const size_t need = size_t(ds->n) * n_frames;
     if (ds->d_lattice.capacity() < 2 * need * 8 || ds->h_lattice.capacity() < 2 * need * 8) {
@@ -1806,7 +1808,7 @@ stage_lattice(aqz_ds* ds, const aqz_chunk_lattice* lat, uint32_t n_frames, hipSt
     uint64_t* d = static_cast<uint64_t*>(ds->d_lattice.get()) + size_t(half) * lattice_half;
     dev->assign(ds->n, nullptr);
     for (uint32_t l = 1; l < ds->n; ++l)
-        for (uint32_t k = 0; k < n_frames; ++k)
+        for (uint32_t k = 0, nk = halving ? n_frames >> l : n_frames; k < nk; ++k)
             h[size_t(l) * n_frames + k] = lat[l].frame_offset_bytes[k] / ds->bpp;
     HIP_TRY(ds, hipMemcpyAsync(d, h, need * 8, hipMemcpyHostToDevice, stream), "lattice upload");
     for (uint32_t l = 1; l < ds->n; ++l)
@@ -1973,6 +1975,209 @@ run_tiled(aqz_ds* ds,
     return AQZ_OK;
 }
 
+// aqz_ds_run_device_volume_tiled (lat == nullptr) and
+// aqz_ds_run_device_volume_chunked: run_tiled's two forms for pyramids whose
+// levels halve XY and Z, through the fused volume kernel.  Level l emits
+// n_frames >> l planes.  All or nothing: the per-frame state machine has no
+// tiled batch form to fall back to.
+int
+run_volume_tiled(aqz_ds* ds,
+                 const char* who,
+                 const void* device_frames,
+                 uint32_t n_frames,
+                 const uint32_t* tile_rows,
+                 const uint32_t* tile_cols,
+                 void* const* device_out_levels,
+                 const aqz_chunk_lattice* lat,
+                 uint8_t* const* device_tile_nonzero,
+                 uint32_t* out_counts,
+                 void* hip_stream)
+{
+    const std::string w(who);
+    if (int rc = settle(ds))
+        return rc;
+    if (ds->transpose)
+        return ds->fail_arg(w + ": input transposition applies to the per-frame path only");
+    ds->last_input = nullptr;
+    if (!device_frames || (!lat && (!device_out_levels || !tile_rows || !tile_cols)))
+        return ds->fail_arg(w + ": null argument");
+    if (ds->n < 2)
+        return ds->fail_arg(w + ": the pyramid has no level to tile");
+    // aqz_ds_run_device_batch's pure_xyz condition, level by level
+    for (uint32_t l = 1; l < ds->n; ++l) {
+        const Level& lv = ds->lv[l];
+        if (!lv.xy || !lv.zh)
+            return ds->fail_arg(w + ": volume pyramids only; level " + std::to_string(l) +
+                                " does not halve XY and Z");
+        if (ds->lv[l - 1].desc.planes % 2 != 0)
+            return ds->fail_arg(w + ": level " + std::to_string(l - 1) +
+                                " has an odd plane count (level " + std::to_string(l) +
+                                " would pass a plane through)");
+        if (lv.has_partial)
+            return ds->fail_arg(w + ": level " + std::to_string(l) +
+                                " holds an earlier plane of the per-frame path");
+    }
+    if (n_frames == 0 || n_frames % (1u << (ds->n - 1)) != 0)
+        return ds->fail_arg(w + ": " + std::to_string(n_frames) +
+                            " planes is not a nonzero multiple of " +
+                            std::to_string(1u << (ds->n - 1)) + ", what level " +
+                            std::to_string(ds->n - 1) + " pairs up");
+    for (uint32_t l = 1; l < ds->n; ++l) {
+        const uint32_t tr = lat ? lat[l].tile_rows : tile_rows[l];
+        const uint32_t tc = lat ? lat[l].tile_cols : tile_cols[l];
+        const void* out = lat ? lat[l].device_base : device_out_levels[l];
+        if (!out || !tr || !tc)
+            return ds->fail_arg(w + ": level " + std::to_string(l) +
+                                " needs an output and a nonzero tile shape");
+        if (lat) {
+            // run_tiled's lattice checks over the level's n_frames >> l planes
+            const aqz_chunk_lattice& c = lat[l];
+            const uint64_t ntiles = uint64_t((ds->lv[l].desc.width + tc - 1) / tc) *
+                                    ((ds->lv[l].desc.height + tr - 1) / tr);
+            const uint64_t tile_bytes = uint64_t(tr) * tc * ds->bpp;
+            if (!c.frame_offset_bytes || c.chunk_stride_bytes % ds->bpp ||
+                c.chunk_stride_bytes < tile_bytes)
+                return ds->fail_arg(w + ": level " + std::to_string(l) +
+                                    ": chunk stride must hold a tile and be a multiple of the "
+                                    "pixel size, and frame offsets are required");
+            const uint64_t extent = (ntiles - 1) * c.chunk_stride_bytes + tile_bytes;
+            for (uint32_t k = 0; k < (n_frames >> l); ++k) {
+                const uint64_t off = c.frame_offset_bytes[k];
+                if (off % ds->bpp || off > c.capacity_bytes || c.capacity_bytes - off < extent)
+                    return ds->fail_arg(w + ": level " + std::to_string(l) + " plane " +
+                                        std::to_string(k) + ": offset " + std::to_string(off) +
+                                        " puts its tiles outside the lattice buffer");
+            }
+        }
+    }
+    // Runs of up to kMaxVolumeLevels levels.  Every run must fit the fused
+    // volume kernel and the tiled plan's limits before anything is queued:
+    // the plans look at addresses and sizes only, so a stand-in for the chain
+    // scratch (aligned, like the allocation) serves here.
+    const uint32_t maxk = aqz::kMaxVolumeLevels;
+    const bool chained = 1 + maxk < ds->n;
+    const auto tiled_outs = [&](uint32_t L, uint32_t k, const std::vector<const uint64_t*>& off,
+                                aqz::TiledOut* t) {
+        for (uint32_t j = 0; j < k; ++j) {
+            const uint32_t l = L + j;
+            uint8_t* nz = device_tile_nonzero ? device_tile_nonzero[l] : nullptr;
+            if (lat)
+                t[j] = { lat[l].device_base, lat[l].tile_rows, lat[l].tile_cols, nz,
+                         off.empty() ? nullptr : off[l], lat[l].chunk_stride_bytes / ds->bpp };
+            else
+                t[j] = { device_out_levels[l], tile_rows[l], tile_cols[l], nz };
+        }
+    };
+    {
+        const void* src = device_frames;
+        void* const stand_in = reinterpret_cast<void*>(uintptr_t(256));
+        const std::vector<const uint64_t*> none;
+        for (uint32_t L = 1, k, planes = n_frames; L < ds->n; L += k, planes >>= k) {
+            k = std::min<uint32_t>(ds->n - L, maxk);
+            aqz::LevelOut o[aqz::kMaxFusedLevels];
+            aqz::TiledOut t[aqz::kMaxFusedLevels];
+            fill_outs(ds, L, k, [](uint32_t) { return nullptr; }, o);
+            tiled_outs(L, k, none, t);
+            if (L + k < ds->n)
+                o[k - 1].ptr = stand_in;
+            const Level& a = ds->lv[L - 1];
+            if (!aqz::volume_supported(ds->dtype, src, a.desc.width, a.desc.height, o, int(k)))
+                return ds->fail_arg(w + ": level " + std::to_string(L - 1) +
+                                    " does not fit the fused volume kernel (" +
+                                    std::to_string(a.desc.width) +
+                                    " px wide: narrower than one vector load, or a misaligned "
+                                    "buffer)");
+            if (!aqz::plan_volume_tiled(ds->dtype, ds->method, src, a.elems(), a.desc.width,
+                                        a.desc.height, o, t, int(k), planes,
+                                        aqz::launch_switches())
+                   .valid)
+                return ds->fail_arg(w + ": levels " + std::to_string(L) + ".." +
+                                    std::to_string(L + k - 1) +
+                                    ": misaligned output, or units, padded sides or zero-fill "
+                                    "items past the launch limits");
+            src = stand_in;
+        }
+    }
+    if (int rc = bind_device(ds))
+        return rc;
+    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ds->stream;
+    std::vector<const uint64_t*> d_off;
+    int half = -1;
+    if (lat)
+        if (int rc = stage_lattice(ds, lat, n_frames, stream, &d_off, &half, true))
+            return rc;
+    // as in run_tiled: the staged half's event on every way out
+    struct LatticeGuard
+    {
+        aqz_ds* ds;
+        int half;
+        hipStream_t stream;
+        ~LatticeGuard()
+        {
+            if (half >= 0)
+                (void)hipEventRecord(ds->lattice_done[half], stream);
+        }
+    } lattice_guard{ ds, half, stream };
+    // A run that feeds another also writes its last level row-major into one
+    // half of d_chain (alternating), ordered behind the handle's previous deep
+    // batch by chain_done — run_tiled's scheme.  The first chained level is
+    // the largest.
+    if (chained) {
+        if (ds->chain_done)
+            HIP_TRY(ds, hipStreamWaitEvent(stream, ds->chain_done, 0), "hipStreamWaitEvent chain");
+        else
+            HIP_TRY(ds, ds->chain_done.create(), "event");
+    }
+    struct ChainGuard
+    {
+        aqz_ds* ds;
+        hipStream_t stream;
+        bool on;
+        ~ChainGuard()
+        {
+            if (on)
+                (void)hipEventRecord(ds->chain_done, stream);
+        }
+    } chain_guard{ ds, stream, chained };
+    if (chained) {
+        const size_t chain_half = size_t(n_frames >> maxk) * ds->lv[maxk].bytes;
+        if (ds->d_chain.capacity() < 2 * chain_half) {
+            HIP_TRY(ds, hipStreamSynchronize(stream), "hipStreamSynchronize");
+            HIP_TRY(ds, ds->d_chain.reserve(2 * chain_half), "hipMalloc chain");
+        }
+    }
+    const void* src = device_frames;
+    uint32_t planes = n_frames;
+    for (uint32_t L = 1, run = 0; L < ds->n; ++run) {
+        const uint32_t k = std::min<uint32_t>(ds->n - L, maxk);
+        const bool feeds = L + k < ds->n;
+        aqz::LevelOut o[aqz::kMaxFusedLevels];
+        aqz::TiledOut t[aqz::kMaxFusedLevels];
+        fill_outs(ds, L, k, [](uint32_t) { return nullptr; }, o);
+        tiled_outs(L, k, d_off, t);
+        void* chain = ds->d_chain.bytes() + (run & 1) * (ds->d_chain.capacity() / 2);
+        if (feeds)
+            o[k - 1].ptr = chain;
+        const Level& a = ds->lv[L - 1];
+        const hipError_t e =
+          aqz::launch_volume_tiled(ds->dtype, ds->method, src, a.elems(), a.desc.width,
+                                   a.desc.height, o, t, int(k), planes, stream);
+        if (e != hipSuccess)
+            return e == hipErrorInvalidValue ? ds->fail_arg(w + ": unsupported geometry")
+                                             : ds->fail(e, "batch tiled volume");
+        src = chain;
+        planes >>= k;
+        L += k;
+    }
+    for (uint32_t l = 0; l < ds->n; ++l) {
+        ds->lv[l].count += n_frames >> l;
+        if (out_counts)
+            out_counts[l] = n_frames >> l;
+    }
+    ds->last_batch_kind = 5;
+    return AQZ_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -2015,6 +2220,50 @@ aqz_ds_run_device_batch_chunked(aqz_ds* ds,
             return ds->fail_arg("run_device_batch_chunked: null lattices");
         return run_tiled(ds, "run_device_batch_chunked", device_frames, n_frames, nullptr,
                          nullptr, nullptr, lattices, device_tile_nonzero, out_counts, hip_stream);
+    } catch (...) {
+        return ABI_GUARD_FAIL(ds);
+    }
+}
+
+int
+aqz_ds_run_device_volume_tiled(aqz_ds* ds,
+                               const void* device_frames,
+                               uint32_t n_frames,
+                               const uint32_t* tile_rows,
+                               const uint32_t* tile_cols,
+                               void* const* device_out_levels,
+                               uint8_t* const* device_tile_nonzero,
+                               uint32_t* out_counts,
+                               void* hip_stream)
+{
+    try {
+        if (!ds)
+            return AQZ_INVALID_ARGUMENT;
+        return run_volume_tiled(ds, "run_device_volume_tiled", device_frames, n_frames, tile_rows,
+                                tile_cols, device_out_levels, nullptr, device_tile_nonzero,
+                                out_counts, hip_stream);
+    } catch (...) {
+        return ABI_GUARD_FAIL(ds);
+    }
+}
+
+int
+aqz_ds_run_device_volume_chunked(aqz_ds* ds,
+                                 const void* device_frames,
+                                 uint32_t n_frames,
+                                 const aqz_chunk_lattice* lattices,
+                                 uint8_t* const* device_tile_nonzero,
+                                 uint32_t* out_counts,
+                                 void* hip_stream)
+{
+    try {
+        if (!ds)
+            return AQZ_INVALID_ARGUMENT;
+        if (!lattices)
+            return ds->fail_arg("run_device_volume_chunked: null lattices");
+        return run_volume_tiled(ds, "run_device_volume_chunked", device_frames, n_frames, nullptr,
+                                nullptr, nullptr, lattices, device_tile_nonzero, out_counts,
+                                hip_stream);
     } catch (...) {
         return ABI_GUARD_FAIL(ds);
     }

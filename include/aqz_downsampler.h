@@ -509,6 +509,59 @@ int aqz_ds_run_device_batch_chunked(aqz_ds* ds,
                                     void* hip_stream);
 
 /*
+ * aqz_ds_run_device_batch_tiled / _chunked for volume pyramids: every level
+ * halves X, Y and Z (a 3-D stack, the reference's 3-D multiscale stream).
+ * The results are those of aqz_ds_run_device_batch on the same handle and
+ * planes when it takes the fused volume path (aqz_ds_last_batch_kind 2):
+ * level L emits n_frames >> L planes, `out_counts` reports that and the
+ * handle's per-level counts advance the same way.  The k-th emitted plane of
+ * level L is written in the tile layout aqz_ds_run_device_batch_tiled
+ * documents — planes back to back in `device_out_levels[L]`, or, for the
+ * chunked form, tile t at lattices[L].frame_offset_bytes[k] + t *
+ * chunk_stride_bytes, where frame_offset_bytes has n_frames >> L entries
+ * (aqz_chunk_frame_offsets on level L's own dimensions).  One fused volume
+ * kernel per two levels writes them from registers and its first waves zero
+ * the tile overhang; no row-major pass, no tiling pass.
+ * `device_tile_nonzero[L]` (optional, as there) receives one flag byte per
+ * tile per emitted plane (flag slots = 1: cleared by a fill queued ahead of
+ * the kernel, set to 1 by the waves that store a nonzero byte), the layout
+ * aqz_zarr_shard_chunk_has_data_device takes with flag_slots = 1.
+ * Accepted when every level halves XY and Z, every level above the last has
+ * an even plane count, no level holds an earlier plane of the per-frame
+ * path, `n_frames` is a nonzero multiple of 2^(n_levels-1), every level that
+ * starts a run of two (0, 2, 4, ...) is at least one 16-byte load wide, tile
+ * shapes are nonzero and no input transposition is set.  Anything else —
+ * and a lattice that fails aqz_ds_run_device_batch_chunked's checks, a
+ * launch of 2^31 or more units or 2^32 or more zero-fill rows — is
+ * AQZ_INVALID_ARGUMENT with a message naming the level, before anything is
+ * queued; there is no fallback path.  aqz_ds_run_device_batch_tiled and
+ * _chunked keep refusing volume pyramids.
+ * Stream rules as for the 2-D calls: everything is queued on `hip_stream`
+ * (NULL = the handle's stream) and the call does not wait on the host, except
+ * the call that grows scratch.  Pyramids deeper than 2 levels chain runs
+ * through the same handle scratch, ordered behind the handle's previous deep
+ * batch by an event wait; the chunked form stages its offsets through the
+ * same two pinned halves (a third call in flight waits for the first).
+ */
+int aqz_ds_run_device_volume_tiled(aqz_ds* ds,
+                                   const void* device_frames,
+                                   uint32_t n_frames,
+                                   const uint32_t* tile_rows,
+                                   const uint32_t* tile_cols,
+                                   void* const* device_out_levels,
+                                   uint8_t* const* device_tile_nonzero,
+                                   uint32_t* out_counts,
+                                   void* hip_stream);
+
+int aqz_ds_run_device_volume_chunked(aqz_ds* ds,
+                                     const void* device_frames,
+                                     uint32_t n_frames,
+                                     const aqz_chunk_lattice* lattices,
+                                     uint8_t* const* device_tile_nonzero,
+                                     uint32_t* out_counts,
+                                     void* hip_stream);
+
+/*
  * Where frames first_frame .. first_frame + n_frames - 1 of an array with
  * storage-order dimensions `dims` (ndims >= 3, the last two Y and X) put
  * their tile 0 in a lattice of chunk buffers `*chunk_bytes` apart:
@@ -547,12 +600,14 @@ int aqz_ds_run_host_batch(aqz_ds* ds,
                           uint32_t* out_counts);
 
 /*
- * Diagnostic: the path the last aqz_ds_run_device_batch[_tiled] took —
+ * Diagnostic: the path the last aqz_ds_run_device_batch[_tiled] or
+ * aqz_ds_run_device_volume_tiled / _chunked took —
  * 0 = per-frame state machine, 1 = fused 2-D cascade, 2 = fused volume
  * (XY + Z), 3 = 2-D batch with some level runs on batched single-level
  * kernels (frames narrower than one 16-byte load, or buffers that are not
  * element-aligned; the fused kernels take any other width and offset),
  * 4 = fused 2-D cascade writing chunk tiles (aqz_ds_run_device_batch_tiled),
+ * 5 = fused volume writing chunk tiles (aqz_ds_run_device_volume_tiled),
  * -1 = none.
  */
 int aqz_ds_last_batch_kind(const aqz_ds* ds);
