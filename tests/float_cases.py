@@ -428,3 +428,52 @@ def class_map(dtype, n, h, w, n_levels, method, level, planes=1, geometry=None):
     for p in planted(dtype, n, h, w, n_levels, method, level, planes, geometry):
         out[p.frame, p.y, p.x] = p.name
     return out
+
+
+# ---- zero tiles of a volume ------------------------------------------------------
+
+ZERO_TILE = (8, 16)  # tile rows x columns of the zero-region checks
+
+
+def zero_region_stack(stack):
+    """A copy of a stack of 8 planes (two groups of 4: one level-2 plane each)
+    whose top half is +0.0 and whose bottom left quarter is -0.0, through all
+    planes.  Planes 0-1 carry one 2 x 2 window of -0.0 at (2, 2): level 1's
+    plane 0 gets one -0.0 at (1, 1) among +0.0.  Planes 4-7 carry one 4 x 4
+    window at (4, 4): level 2's plane 1 gets one -0.0 at (1, 1).  The classes
+    stay in the bottom right quarter."""
+    f = np.array(stack)
+    n, h, w = f.shape
+    assert n == 8 and h >= 64 and w >= 128
+    f[:, : h // 2] = 0.0
+    f[:, h // 2:, : w // 2] = -0.0
+    f[0:2, 2:4, 2:4] = -0.0
+    f[4:8, 4:8, 4:8] = -0.0
+    return f
+
+
+def check_zero_region_tiles(dtype, level, tiles, nonzero, level_h, level_w):
+    """`tiles` (planes, n_tiles, tr, tc) and `nonzero` (planes, n_tiles) of
+    `level` (1 or 2) of a zero_region_stack under ZERO_TILE hold what the stack
+    was built for: whole tiles of +0.0 with flag 0, whole tiles of -0.0 with
+    flag 1 (the scan is byte-wise), and on plane level - 1 a tile 0 whose only
+    nonzero bytes are one -0.0 at (1, 1)."""
+    tr, tc = ZERO_TILE
+    ut = np.dtype(f"u{np.dtype(dtype).itemsize}")
+    sign = ut.type(1 << (8 * ut.itemsize - 1))
+    ntx = -(-level_w // tc)
+    k = level - 1
+    bits = np.ascontiguousarray(tiles).view(ut)
+    b0 = bits[k, 0].reshape(-1)
+    assert nonzero[k, 0] and (b0 != 0).sum() == 1 and b0[tc + 1] == sign, \
+        f"level {level}: tile 0 of plane {k} is not one -0.0 among +0.0"
+    # the tile right of it, and tile 0 of a plane without a window: +0.0, flag 0
+    assert not nonzero[k, 1] and not bits[k, 1].any()
+    p = 1 - k  # level 1's plane 1 (planes 2-3), level 2's plane 0 (one -0.0 in eight)
+    assert not nonzero[p, 0] and not bits[p, 0].any()
+    # the first tile of the last full tile row, in the bottom left quarter: -0.0 alone
+    ty = level_h // tr - 1
+    assert ty * tr >= (level_h + 1) // 2 and tc <= level_w // 2
+    t = ty * ntx
+    assert all(nonzero[p, t] and (bits[p, t] == sign).all() for p in range(bits.shape[0])), \
+        f"level {level}: tile {t} is not -0.0 alone"

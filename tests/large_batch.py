@@ -48,9 +48,13 @@ def modulus(dtype):
 
 
 # family: row (aqz_ds_run_device_batch, 2-D), volume (kind 2), zpath (kind 0),
-#         tiled (aqz_ds_run_device_batch_tiled), lattice (..._chunked)
+#         tiled (aqz_ds_run_device_batch_tiled), lattice (..._chunked),
+#         volume_tiled (aqz_ds_run_device_volume_tiled, kind 5),
+#         volume_lattice (..._volume_chunked)
 # depth:  shallow = the input passes 2^32 bytes; deep = level 1's output does
+# tile:   (rows, columns) of every level, or a list with one per level
 Case = namedtuple("Case", "id family name geo dtype method kind depth tile")
+VOLUME_FAMILIES = ("volume", "volume_tiled", "volume_lattice")
 
 BATCH_2D = ["2d", "2d_generic", "2d_narrow", "2d_oddw_deep", "2d_six", "2d_band_staged",
             "2d_wide_misaligned", "2d_band8_aligned", "2d_band6_edge_rows", "2d_band_segments",
@@ -63,6 +67,19 @@ TILED_SHAPES = [(1000, 600, 4, 64, 128), (512, 512, 4, 3, 5)]   # of TILED_CASES
 # test_time_chunks)
 LATTICE_DIMS = [(2, 0, 3, 1), (0, 384, 128, 1), (0, 520, 96, 1)]
 LATTICE_GEO = [(520, 384, 0), (260, 192, 0), (130, 96, 0)]   # the planner's, T unbounded
+# tiled volumes: 72 x 40 x 8 under 8 x 16 tiles (level 1 is 36 x 20: four rows
+# of overhang the units do not reach), under 64 x 64 tiles (deep: a 4096-byte
+# padded u8 plane against 2 x 2880 bytes of input), and volume_tiled_cases'
+# column zero-fill shape (512 x 8 x 4 under 2 x 384 tiles)
+VOLUME_TILED_NAME = "3d_fused_many_groups_edge"
+VOLUME_TILED_TILE, VOLUME_TILED_DEEP_TILE = (8, 16), (64, 64)
+COLUMN_FILL_GEO = [(512, 8, 4), (256, 4, 2), (128, 2, 1)]
+COLUMN_FILL_TILE = (2, 384)
+# volume lattice: 200 x 61 x 8 u16; level 1 is 4 x 31 x 100 in chunks of
+# 2 x 20 x 80 (ragged in Y and X, a padded plane of 12800 bytes), level 2 is
+# 2 x 16 x 50 in chunks of 2 x 12 x 32
+VOLUME_LATTICE_NAME = "3d_fused_edge"
+VOLUME_LATTICE_SHAPES = [None, (2, 20, 80), (2, 12, 32)]   # (z, y, x) chunk per level
 
 
 def _dn(d):
@@ -101,6 +118,19 @@ def _table():
                               halving_geometry(w, h, nl), dt, 1, 4, "deep", (tr, tc)))
     cases.append(Case("lattice-520x384-uint16-m1", "lattice", "lattice", LATTICE_GEO, np.uint16,
                       1, 4, "deep", (LATTICE_DIMS[1][2], LATTICE_DIMS[2][2])))
+    geo = BATCH_GEOMETRIES[VOLUME_TILED_NAME][0]
+    for name, g, tile in ((VOLUME_TILED_NAME, geo, VOLUME_TILED_TILE),
+                          ("column_fill", COLUMN_FILL_GEO, COLUMN_FILL_TILE)):
+        for dt, m in ((np.uint8, 1), (np.uint16, 1), (np.float32, 1), (np.uint16, 0)):
+            cases.append(Case(f"vtiled-{name}-{tile[0]}x{tile[1]}-{_dn(dt)}-m{m}", "volume_tiled",
+                              f"vtiled-{name}", g, dt, m, 5, "shallow", tile))
+    tile = VOLUME_TILED_DEEP_TILE
+    cases.append(Case(f"deep-vtiled-{VOLUME_TILED_NAME}-{tile[0]}x{tile[1]}-uint8-m1",
+                      "volume_tiled", f"vtiled-{VOLUME_TILED_NAME}", geo, np.uint8, 1, 5, "deep",
+                      tile))
+    cases.append(Case(f"vlattice-{VOLUME_LATTICE_NAME}-uint16-m1", "volume_lattice",
+                      f"vlattice-{VOLUME_LATTICE_NAME}", BATCH_GEOMETRIES[VOLUME_LATTICE_NAME][0],
+                      np.uint16, 1, 5, "deep", [None] + [s[1:] for s in VOLUME_LATTICE_SHAPES[1:]]))
     return cases
 
 
@@ -122,7 +152,7 @@ def bpp(case):
 def group_planes(case):
     """Planes that share one tag: 1 for 2-D pyramids, 2^(levels - 1) for the
     fused volume, one stack for the per-frame Z path."""
-    if case.family == "volume":
+    if case.family in VOLUME_FAMILIES:
         return 1 << (len(case.geo) - 1)
     if case.family == "zpath":
         return case.geo[0][2]
@@ -131,11 +161,15 @@ def group_planes(case):
 
 def per_group(case, level):
     """Level-`level` frames one plane group emits."""
-    if case.family == "volume":
+    if case.family in VOLUME_FAMILIES:
         return group_planes(case) >> level
     if case.family == "zpath":
         return case.geo[level][2]
     return 1
+
+
+def tile_of(case, level):
+    return case.tile[level] if isinstance(case.tile, list) else case.tile
 
 
 def frame_elems(case, level):
@@ -143,7 +177,7 @@ def frame_elems(case, level):
     chunk-tiled outputs."""
     w, h, _ = case.geo[level]
     if level and case.tile:
-        tr, tc = case.tile
+        tr, tc = tile_of(case, level)
         return (-(-h // tr) * tr) * (-(-w // tc) * tc)
     return w * h
 
@@ -163,6 +197,8 @@ def frames_for(case):
     unit = max(1, case.geo[0][2])
     if case.family == "lattice":
         unit = LATTICE_DIMS[0][2]
+    if case.family == "volume_lattice":   # whole chunk layers at every level
+        unit = math.lcm(unit, *[s[0] << L for L, s in enumerate(VOLUME_LATTICE_SHAPES) if L])
     return -(-n // unit) * unit
 
 
@@ -177,7 +213,7 @@ def flag_bytes_bound(case, level):
     """Zero-scan flag bytes per frame, at most: a slot covers at least one
     element of its tile."""
     w, h, _ = case.geo[level]
-    tr, tc = case.tile
+    tr, tc = tile_of(case, level)
     return (-(-h // tr)) * (-(-w // tc)) * tr * tc
 
 
@@ -188,8 +224,8 @@ def need_bytes(case):
     total = n * frame_bytes(case, 0)
     for L in range(1, len(case.geo)):
         total += level_frames(case, L, n) * frame_bytes(case, L) + PAD
-        if case.family == "tiled":
-            total += n * flag_bytes_bound(case, L) + PAD
+        if case.family in ("tiled", "volume_tiled"):
+            total += level_frames(case, L, n) * flag_bytes_bound(case, L) + PAD
     return total + 4 * SLAB_BYTES + (64 << 20)
 
 
@@ -246,8 +282,11 @@ def expected_levels(oracle, case):
 
 def tiled_expectation(oracle, case, level, e_level, tag):
     """oracle.tile_frame of E[level] + tag: (tiles, nonzero flags)."""
-    shifted = (e_level.astype(np.int64) + tag).astype(case.dtype)
-    return oracle.tile_frame(shifted, *case.tile)
+    if np.dtype(case.dtype).kind == "f":    # a Mean's level holds fractions: exact in float32
+        shifted = e_level + np.asarray(tag, case.dtype)
+    else:
+        shifted = (e_level.astype(np.int64) + tag).astype(case.dtype)
+    return oracle.tile_frame(shifted, *tile_of(case, level))
 
 
 # ---- device side (torch is plumbing only) -----------------------------------
@@ -376,7 +415,9 @@ def lz4_chunks():
 
 _GROUPS = {}
 CHILD_TIMEOUT_S = {"row": 900, "volume": 420, "deep": 420, "tiled": 420, "filter": 420,
-                   "crc": 300, "lz4": 420}
+                   "crc": 300, "lz4": 420,
+                   # ten cases, 8 s in all when measured (profiles/volume_tiled_tests/)
+                   "volume_tiled": 300}
 
 
 def run_group(group):

@@ -11,7 +11,7 @@ A failed comparison (AssertionError) is the case's "error" and the next case
 runs.  Anything else (a HIP error, a fault reported by the runtime) ends the
 child at once with status 3, so nothing more is launched on that card.
 
-Usage: large_batch_child.py --group row|volume|deep|tiled|filter|crc|lz4
+Usage: large_batch_child.py --group row|volume|deep|tiled|volume_tiled|filter|crc|lz4
 """
 import argparse
 import json
@@ -211,11 +211,143 @@ def run_lattice(aqz, case):
     return kind, launches
 
 
+def volume_tiled_expected(case, e, L):
+    """tiled_expected for the level's planes of one plane group: (per, nt, tr,
+    tc) tiles of tag 0 and mask, (per, nt) flags of tag 0 and of any tag above."""
+    per = lb.per_group(case, L)
+    t0, f0, t1, f1 = [], [], [], []
+    for j in range(per):
+        a, fa = lb.tiled_expectation(oracle, case, L, e[L][j], 0)
+        b, fb = lb.tiled_expectation(oracle, case, L, e[L][j], 1)
+        t0.append(a), f0.append(fa), t1.append(b), f1.append(fb)
+    t0, t1 = np.stack(t0), np.stack(t1)
+    mask = (t1 != t0).astype(case.dtype)
+    return (dev_level(case, t0), dev_level(case, mask),
+            torch.from_numpy(np.stack(f0)).to("cuda"), torch.from_numpy(np.stack(f1)).to("cuda"))
+
+
+def run_volume_tiled(aqz, case):
+    """aqz_ds_run_device_volume_tiled with flags: level L's n >> L planes,
+    a plane group's planes sharing its tag."""
+    n = lb.frames_for(case)
+    need_memory(lb.need_bytes(case))
+    e = lb.expected_levels(oracle, case)
+    tr, tc = case.tile
+    nl = len(case.geo)
+    gp = lb.group_planes(case)
+    assert n % gp == 0
+    d_in = lb.build_batch(torch, case, n)
+    nts, sizes, fsizes, outs, flags = [0], [0], [0], [None], [None]
+    for L in range(1, nl):
+        w, h, _ = case.geo[L]
+        nt = (-(-h // tr)) * (-(-w // tc))
+        assert nt * tr * tc == lb.frame_elems(case, L) and lb.level_frames(case, L, n) == n >> L
+        nts.append(nt)
+        sizes.append((n >> L) * lb.frame_bytes(case, L))
+        fsizes.append((n >> L) * nt)
+        outs.append(lb.poisoned(torch, sizes[L]))
+        flags.append(lb.poisoned(torch, fsizes[L]))
+    ds = aqz.Downsampler(case.geo, case.dtype, case.method)
+    try:
+        aqz.debug_launch_log()
+        counts = ds.run_device_volume_tiled(
+            d_in.data_ptr(), n, [None] + [(tr, tc)] * (nl - 1),
+            [0] + [o.data_ptr() for o in outs[1:]], [0] + [f.data_ptr() for f in flags[1:]],
+            launch_stream())
+        torch.cuda.synchronize()
+        kind = ds.last_batch_kind()
+    finally:
+        ds.close()
+    launches = aqz.debug_launch_log()
+    del d_in
+    assert counts == [n >> L for L in range(nl)], counts
+    vt = lb.torch_view_dtype(torch, case.dtype)
+    tags = lb.device_tags(torch, case, n // gp)
+    for L in range(1, nl):
+        per = lb.per_group(case, L)
+        t0, mask, f0, f1 = volume_tiled_expected(case, e, L)
+        poison_kept(outs[L], sizes[L], f"level {L} tiles")
+        poison_kept(flags[L], fsizes[L], f"level {L} flags")
+        got = outs[L][:sizes[L]].view(vt).view(n >> L, nts[L], tr, tc)
+        lb.compare_frames(torch, got, t0, mask, tags, per, f"{case.id} level {L} tiles")
+        fl = flags[L][:fsizes[L]].view(n // gp, per, nts[L])
+        assert bool((fl <= 1).all()), f"level {L}: a flag byte is neither 0 nor 1"
+        want = torch.where((tags == 0).view(-1, 1, 1), f0.unsqueeze(0), f1.unsqueeze(0))
+        bad = ((fl != 0) != want).flatten(1).any(1)
+        if bool(bad.any()):
+            k = int(torch.nonzero(bad)[0])
+            raise AssertionError(f"{case.id} level {L}: zero-scan flags of {int(bad.sum())} plane "
+                                 f"groups differ, first group {k} (tag {int(tags[k])})")
+    return kind, launches
+
+
+def run_volume_lattice(aqz, case):
+    """aqz_ds_run_device_volume_chunked into whole chunk layers: every byte of
+    every lattice is owned by a plane of the batch."""
+    import volume_tiled_cases as vc
+    n = lb.frames_for(case)
+    need_memory(lb.need_bytes(case))
+    e = lb.expected_levels(oracle, case)
+    nl = len(case.geo)
+    b = lb.bpp(case)
+    gp = lb.group_planes(case)
+    shapes = lb.VOLUME_LATTICE_SHAPES
+    lats, bufs, caps, nts = [None], [None], [0], [0]
+    for L in range(1, nl):
+        cz, tr, tc = shapes[L]
+        nf = n >> L
+        # oracle addressing (array.dimensions.cpp:232-314), never the product's
+        o, cb, layer = oracle.chunk_frame_offsets(vc.chunk_dims(L, case.geo, shapes), b, 0, nf)
+        w, h, _ = case.geo[L]
+        nt = (-(-h // tr)) * (-(-w // tc))
+        assert cb == cz * tr * tc * b and layer == nt * cb and nf % cz == 0
+        assert o == [(k // cz) * layer + (k % cz) * tr * tc * b for k in range(nf)]
+        cap = (max(o) // layer + 1) * layer
+        assert cap == nf * lb.frame_bytes(case, L)
+        caps.append(cap)
+        nts.append(nt)
+        bufs.append(lb.poisoned(torch, cap))
+        lats.append((bufs[L].data_ptr(), cap, tr, tc, cb, o))
+    assert caps[1] > 1 << 32
+    d_in = lb.build_batch(torch, case, n)
+    ds = aqz.Downsampler(case.geo, case.dtype, case.method, device=0)
+    try:
+        aqz.debug_launch_log()
+        counts = ds.run_device_volume_chunked(d_in.data_ptr(), n, lats, None, launch_stream())
+        torch.cuda.synchronize()
+        kind = ds.last_batch_kind()
+    finally:
+        ds.close()
+    launches = aqz.debug_launch_log()
+    del d_in
+    assert counts == [n >> L for L in range(nl)], counts
+    vt = lb.torch_view_dtype(torch, case.dtype)
+    for L in range(1, nl):
+        cz, tr, tc = shapes[L]
+        per = lb.per_group(case, L)
+        assert cz % per == 0
+        q = cz // per                      # plane groups per chunk layer
+        layers = (n >> L) // cz
+        t0, mask, _, _ = volume_tiled_expected(case, e, L)
+        poison_kept(bufs[L], caps[L], f"level {L}")
+        # a layer: (chunk, group in chunk, plane of the group, rows, cols)
+        got = bufs[L][:caps[L]].view(vt).view(layers, nts[L], q, per, tr, tc)
+        tags = lb.device_tags(torch, case, n // gp).view(layers, 1, 1, q, 1, 1, 1)
+        want0 = t0.permute(1, 0, 2, 3).reshape(1, nts[L], 1, per, tr, tc)
+        m = mask.permute(1, 0, 2, 3).reshape(1, nts[L], 1, per, tr, tc)
+        lb.compare_frames(torch, got, want0, m, tags, 1, f"{case.id} level {L} lattice")
+    return kind, launches
+
+
 def run_case(aqz, case):
     if case.family == "tiled":
         return run_tiled(aqz, case)
     if case.family == "lattice":
         return run_lattice(aqz, case)
+    if case.family == "volume_tiled":
+        return run_volume_tiled(aqz, case)
+    if case.family == "volume_lattice":
+        return run_volume_lattice(aqz, case)
     return run_pyramid(aqz, case)
 
 
@@ -224,6 +356,7 @@ PYRAMID_GROUPS = {
     "volume": lambda: lb.select("volume", "shallow"),
     "deep": lambda: lb.select("row", "deep") + lb.select("volume", "deep") + lb.select("zpath"),
     "tiled": lambda: lb.select("tiled") + lb.select("lattice"),
+    "volume_tiled": lambda: lb.select("volume_tiled") + lb.select("volume_lattice"),
 }
 
 

@@ -6,7 +6,7 @@ process of its own: the test starts
 this file (a new process, never exec'd) with one rule's environment plus
 AQZ_LAUNCH_LOG=1.
 
-  --family cascade|tiled|volume|codec
+  --family cascade|tiled|volume|volume_tiled|codec
 
 runs that family's fixed case list against the oracle, byte for byte for
 every dtype (floats and NaN payloads included: the alternative launches keep
@@ -158,6 +158,15 @@ def check_launch(rec):
                     else -(-units // rec["wpb"]))
             if rec["main_blocks"] < need:
                 err.append("tiled cascade blocks do not cover the units")
+    elif fam == "volume_tiled":
+        if waves != rec["wpb"] or rec["zwaves"] % rec["wpb"]:
+            err.append("tiled volume block / zero-fill waves do not match wpb")
+        if grid != rec["zwaves"] // rec["wpb"] + rec["main_blocks"]:
+            err.append("tiled volume grid is not zero-fill blocks + unit blocks")
+        if rec["main_blocks"] * rec["wpb"] < rec["units"]:
+            err.append("tiled volume blocks do not cover the units")
+        if (rec["zwaves"] > 0) != (rec["zitems"] > 0):
+            err.append("zero-fill waves without items, or items without waves")
     elif fam == "volume":
         if block != 256:
             err.append("volume block is not 256")
@@ -322,6 +331,58 @@ class Runner:
                             poison += p
                 self.report(tiled_id(case, method), differing, poison, 0, error)
 
+    # ---- chunk-tiled volumes ---------------------------------------------------
+
+    def volume_tiled(self):
+        """aqz_ds_run_device_volume_tiled on volume_tiled_cases.ZROWS_CASES: tiles, flags
+        and the PAD bytes behind both against the oracle."""
+        import volume_tiled_cases as vc
+        from gpu_util import empty_device, from_device, launch_stream, to_device
+
+        for case in vc.ZROWS_CASES:
+            w, h, planes, levels, dt, _, _, _ = case
+            geo = vc.volume_geo(w, h, planes, levels)
+            tiles = vc.case_tiles(case)
+            frames = vc.case_frames(case)
+            n = len(frames)
+            d_in = to_device(frames)
+            for method in METHODS:
+                want = vc.expected_tiled(
+                    self.oracle, vc.oracle_planes(self.oracle, geo, dt, method, frames), tiles)
+                outs, flags = [None], [None]
+                for L in range(1, levels):
+                    outs.append(empty_device(want[L][0].nbytes + PAD))
+                    flags.append(empty_device(want[L][1].size + PAD))
+                    outs[L].fill_(POISON)
+                    flags[L].fill_(POISON)
+                ds = self.aqz.Downsampler(geo, dt, method)
+                differing = poison = stray = 0
+                error = None
+                try:
+                    ds.run_device_volume_tiled(d_in.data_ptr(), n, tiles,
+                                               [0] + [o.data_ptr() for o in outs[1:]],
+                                               [0] + [f.data_ptr() for f in flags[1:]],
+                                               launch_stream())
+                    self.torch.cuda.synchronize()
+                    if ds.last_batch_kind() != 5:
+                        error = f"batch kind {ds.last_batch_kind()}, expected 5"
+                        differing = 1
+                except self.aqz.AqzError as e:
+                    error = f"AqzError: {e}"
+                    differing = 1
+                ds.close()
+                for L in range(1, levels):
+                    t, nz = want[L]
+                    raw = from_device(outs[L], np.uint8, (-1,))
+                    d, p = byte_counts(raw[:t.nbytes], t.view(np.uint8).reshape(-1))
+                    fl = from_device(flags[L], np.uint8, (-1,))
+                    d2, p2 = byte_counts(fl[:nz.size], nz.reshape(-1).astype(np.uint8))
+                    differing += d + d2
+                    poison += p + p2
+                    stray += int(np.count_nonzero(raw[t.nbytes:] != POISON) +
+                                 np.count_nonzero(fl[nz.size:] != POISON))
+                self.report(f"{vc.case_id(case)}/m{method}", differing, poison, stray, error)
+
     # ---- blosc filters --------------------------------------------------------
 
     def codec(self):
@@ -350,7 +411,7 @@ class Runner:
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--family", required=True, choices=["cascade", "tiled", "volume", "codec"])
+    ap.add_argument("--family", required=True, choices=["cascade", "tiled", "volume", "volume_tiled", "codec"])
     args = ap.parse_args()
     r = Runner()
     getattr(r, args.family)()

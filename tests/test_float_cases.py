@@ -478,3 +478,32 @@ def test_oracle_replays_reference_float_classes(oracle, geom, dtype, method):
             got = int(frames[L][p.frame][p.y, p.x])
             assert got == expected_bits(f, method, p.ops), (L, p, hex(got))
             check_defining_bits(f, method, p, got)
+
+
+@pytest.mark.parametrize("dtype", FLOATS, ids=["f32", "f64"])
+def test_zero_region_stack_reaches_its_tiles(oracle, dtype):
+    """The stack tests/test_gpu_float_classes.py sends through the tiled
+    volume call: under Mean the oracle's level-1 and level-2 planes, tiled,
+    hold whole tiles of +0.0 (flag 0), whole tiles of -0.0 (flag 1) and a tile
+    whose only nonzero bytes are one -0.0, and the bottom right quarter keeps
+    the planted classes."""
+    geo, n, _ = BATCH_GEOMETRIES["3d_fused"]
+    w, h, planes = geo[0]
+    edge = fc.edge_frames(dtype, n, h, w, len(geo), planes, geometry=geo)
+    stack = fc.zero_region_stack(edge)
+    ut = np.dtype(f"u{np.dtype(dtype).itemsize}")
+    assert np.array_equal(stack[:, h // 2:, w // 2:].view(ut), edge[:, h // 2:, w // 2:].view(ut))
+    lv = oracle_levels(oracle, geo, dtype, fc.MEAN, stack)
+    plain = oracle_levels(oracle, geo, dtype, fc.MEAN, edge)
+    tr, tc = fc.ZERO_TILE
+    for L in (1, 2):
+        gw, gh, _ = geo[L]
+        t = [oracle.tile_frame(p, tr, tc) for p in lv[L]]
+        fc.check_zero_region_tiles(dtype, L, np.stack([a for a, _ in t]),
+                                   np.stack([b for _, b in t]), gh, gw)
+        # outputs fed by the bottom right quarter alone are the edge stack's own
+        y0, x0 = (h // 2 >> L) + 1, (w // 2 >> L) + 1
+        for a, b in zip(lv[L], plain[L]):
+            assert np.array_equal(a[y0:, x0:].view(ut), b[y0:, x0:].view(ut))
+        kept = fc.class_map(dtype, n, h, w, len(geo), fc.MEAN, L, planes, geometry=geo)[:, y0:, x0:]
+        assert (kept != None).any(), f"level {L}: no planted class left"  # noqa: E711

@@ -23,7 +23,9 @@ by tests/test_float_cases.py), two frames or one stack each:
   +0.0 (flag 0), whole tiles of -0.0 (flag 1: the scan is byte-wise) and a
   tile whose only nonzero bytes are one -0.0;
 * the fused volume kernel (kind 2) and the Z state machine (kind 0, and a
-  Z-only stack through add_frame).
+  Z-only stack through add_frame);
+* the fused volume kernel writing chunk tiles (kind 5), with the same three
+  kinds of zero tile on a plane of level 1 and on one of level 2.
 """
 import numpy as np
 import pytest
@@ -282,3 +284,107 @@ def test_tiled_batch(aqz, oracle, case, dtype, method):
                 inside = oracle.tile_frame(np.ones_like(ref[0]), tr, tc)[0][last_row_left] != 0
                 assert want_nz[last_row_left] and \
                     (want_t.view(ut)[last_row_left][inside] == nz_bit).all()
+
+
+# ---- the tiled volume call -------------------------------------------------------
+
+# tile rows x columns per geometry: level edges inside tiles (200 / 201 x 61
+# gives 100 / 101 x 31 and 50 / 51 x 16), lane columns across tile edges (25),
+# and float_cases' zero-region shape on 3d_fused
+VOLUME_TILES = {"3d_fused": fc.ZERO_TILE, "3d_fused_edge": (5, 25), "3d_fused_oddw": (16, 48),
+                "3d_fused_one_level": (3, 40)}
+
+
+def run_volume_tiled_poisoned(aqz, geo, dtype, method, frames, tr, tc):
+    """aqz_ds_run_device_volume_tiled with flags into poisoned tiles and flag
+    bytes, PAD poisoned bytes behind each: (tiles (planes, nt, tr, tc), flags
+    (planes, nt)) per level."""
+    torch = torch_cuda()
+    n = len(frames)
+    bpp = np.dtype(dtype).itemsize
+    d_in = to_device(frames)
+    outs, flags, nts = [None], [None], [None]
+    for L, (w, h, _) in enumerate(geo[1:], 1):
+        nt = (-(-h // tr)) * (-(-w // tc))
+        outs.append(empty_device((n >> L) * nt * tr * tc * bpp + PAD))
+        flags.append(empty_device((n >> L) * nt + PAD))
+        nts.append(nt)
+        outs[L].fill_(POISON)
+        flags[L].fill_(POISON)
+    ds = aqz.Downsampler(geo, dtype, method)
+    try:
+        counts = ds.run_device_volume_tiled(
+            d_in.data_ptr(), n, [None] + [(tr, tc)] * (len(geo) - 1),
+            [0] + [o.data_ptr() for o in outs[1:]], [0] + [f.data_ptr() for f in flags[1:]],
+            launch_stream())
+        torch.cuda.synchronize()
+        assert ds.last_batch_kind() == 5
+        assert counts == [n >> L for L in range(len(geo))]
+    finally:
+        ds.close()
+    got = [None]
+    for L in range(1, len(geo)):
+        raw = from_device(outs[L], np.uint8, (-1,))
+        fraw = from_device(flags[L], np.uint8, (-1,))
+        assert (raw[-PAD:] == POISON).all() and (fraw[-PAD:] == POISON).all(), \
+            f"level {L}: bytes behind the output were written"
+        fl = fraw[:-PAD].reshape(n >> L, nts[L])
+        assert np.isin(fl, (0, 1)).all(), f"level {L}: a flag byte is neither 0 nor 1"
+        got.append((raw[:-PAD].view(dtype).reshape(n >> L, nts[L], tr, tc), fl.astype(bool)))
+    return got
+
+
+def check_volume_tiled(aqz, oracle, geo, dtype, method, frames, tr, tc, ctx, kept=None):
+    """Tiles as unsigned integers against the oracle's planes tiled by
+    oracle.tile_frame; a mismatch is named untiled, with its planted class
+    (`kept(level, y, x)`: whether the element still holds the edge stack's)."""
+    n = len(frames)
+    w, h, planes = geo[0]
+    expected = oracle_stream(oracle, geo, dtype, method, frames)
+    got = run_volume_tiled_poisoned(aqz, geo, dtype, method, frames, tr, tc)
+    ut = np.dtype(f"u{np.dtype(dtype).itemsize}")
+    want = [None]
+    for L in range(1, len(geo)):
+        assert len(expected[L]) == n >> L
+        t = [oracle.tile_frame(p, tr, tc) for p in expected[L]]
+        want_t, want_nz = np.stack([a for a, _ in t]), np.stack([b for _, b in t])
+        want.append((want_t, want_nz))
+        g, fl = got[L]
+        if not np.array_equal(g.view(ut), want_t.view(ut)):
+            k, ti, r, c = (int(v) for v in np.argwhere(g.view(ut) != want_t.view(ut))[0])
+            ntx = -(-geo[L][0] // tc)
+            y, x = ti // ntx * tr + r, ti % ntx * tc + c
+            inside = y < geo[L][1] and x < geo[L][0]
+            cls = (fc.class_map(dtype, n, h, w, len(geo), method, L, planes, geometry=geo)[k, y, x]
+                   if inside and (kept is None or kept(L, y, x)) else None)
+            raise AssertionError(
+                f"{ctx} level {L} plane {k}: tile {ti} element ({r}, {c}) = plane element "
+                f"({y}, {x}), planted class {cls}: got {int(g.view(ut)[k, ti, r, c]):#x}, "
+                f"oracle {int(want_t.view(ut)[k, ti, r, c]):#x}")
+        assert np.array_equal(fl, want_nz), f"{ctx} level {L}: zero scan"
+    return want
+
+
+@pytest.mark.parametrize("name,dtype,method", _cases(VOLUMES))
+def test_volume_tiled_batch(aqz, oracle, name, dtype, method):
+    geo, n, kind = BATCH_GEOMETRIES[name]
+    assert kind == 2 and n == geo[0][2]
+    tr, tc = VOLUME_TILES[name]
+    check_volume_tiled(aqz, oracle, geo, dtype, method, edge_stack(dtype, geo, n), tr, tc,
+                       f"volume tiled {name} {tr}x{tc} {_name(dtype)} m{method}")
+
+
+@pytest.mark.parametrize("dtype", FLOATS, ids=_name)
+def test_volume_tiled_zero_tiles(aqz, oracle, dtype):
+    """float_cases.zero_region_stack under Mean: whole tiles of +0.0 (flag 0),
+    whole tiles of -0.0 (flag 1) and a tile whose only nonzero bytes are one
+    -0.0, on a plane emitted at level 1 and on one emitted at level 2."""
+    geo, n, _ = BATCH_GEOMETRIES["3d_fused"]
+    w, h, _ = geo[0]
+    tr, tc = fc.ZERO_TILE
+    frames = fc.zero_region_stack(edge_stack(dtype, geo, n))
+    want = check_volume_tiled(
+        aqz, oracle, geo, dtype, fc.MEAN, frames, tr, tc, f"volume tiled zero tiles {_name(dtype)}",
+        kept=lambda L, y, x: y > h // 2 >> L and x > w // 2 >> L)
+    for L in (1, 2):
+        fc.check_zero_region_tiles(dtype, L, want[L][0], want[L][1], geo[L][1], geo[L][0])

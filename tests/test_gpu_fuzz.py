@@ -12,7 +12,8 @@ input and output buffers at element-aligned but otherwise arbitrary byte
 offsets (which turns aligned rows into misaligned ones).  Every dtype
 bit-exact, floats through their integer views (assert_parity).  Also:
 chunk-tiled batches with random
-tile shapes, and Z stacks (fused 2x2x2 or the Z state machine)."""
+tile shapes, Z stacks (fused 2x2x2 or the Z state machine), and volume
+pyramids written straight into chunk tiles or a chunk lattice."""
 import os
 import re
 import zlib
@@ -20,6 +21,7 @@ import zlib
 import numpy as np
 import pytest
 
+import volume_tiled_cases as vc
 from gpu_util import (assert_parity, empty_device, from_device, launch_stream,
                       random_frames, to_device, torch_cuda)
 
@@ -223,4 +225,61 @@ def test_fuzz_volume_batch(aqz, oracle, case):
         got = from_device(outs[L], dtype, (n, gh, gw))
         for k, e in enumerate(expected[L]):
             assert_parity(got[k], e, f"{ctx} level {L} frame {k}")
+    ds.close()
+
+
+# 96 and 32 cases; $AQZ_FUZZ_CASES widens or narrows these sweeps in proportion
+N_VOLUME_TILED = max(vc.N_FUZZ_TILED * N_CASES // 256, 1)
+N_VOLUME_CHUNKED = max(vc.N_FUZZ_CHUNKED * N_CASES // 256, 1)
+
+
+@pytest.mark.parametrize("case", range(N_VOLUME_TILED))
+def test_fuzz_volume_tiled(aqz, oracle, case):
+    """aqz_ds_run_device_volume_tiled: volume pyramids of 2-7 levels (one to
+    three chained runs), a tile shape per level, input and tiles at element
+    offsets, flags present or not (volume_tiled_cases.fuzz_tiled_params; what
+    the cases reach is counted in test_volume_tiled_fuzz_cases.py).  Every
+    tile byte, overhang zeros included, every flag, and the poison in front
+    of and behind every buffer.  The generator builds only pyramids the call
+    accepts: a refusal fails the case."""
+    c = vc.fuzz_tiled_params(case)
+    dtype, geo, tiles, n = c["dtype"], c["geo"], c["tiles"], c["n"]
+    frames = vc.fuzz_frames(c, [None] + [t[1] for t in tiles[1:]])
+    want = vc.expected_tiled(oracle, vc.oracle_planes(oracle, geo, dtype, c["method"], frames),
+                             tiles)
+    ctx = (f"case {case}: {np.dtype(dtype).name} m{c['method']} {c['w']}x{c['h']}x{c['planes']} "
+           f"x{c['stacks']} L{c['levels']} tiles {tiles[1:]} in+{c['in_off']} out+{c['out_off'][1:]}")
+    ds = aqz.Downsampler(geo, dtype, c["method"])
+    out = vc.Outputs(geo, dtype, tiles, n, with_flags=c["flags"], offs=c["out_off"])
+    d_in, src = vc.offset_input(frames, c["in_off"])
+    counts = out.run(ds, src)
+    torch_cuda().cuda.synchronize()
+    assert ds.last_batch_kind() == 5, ctx
+    assert counts == [n >> L for L in range(len(geo))], ctx
+    out.check(want, ctx)
+    raw = from_device(d_in, np.uint8, (-1,))
+    assert (raw[-vc.GUARD:] == vc.POISON).all() and \
+        (raw[:c["in_off"] * frames.dtype.itemsize] == vc.POISON).all(), f"{ctx}: input buffer written"
+    ds.close()
+
+
+@pytest.mark.parametrize("case", range(N_VOLUME_CHUNKED))
+def test_fuzz_volume_chunked(aqz, oracle, case):
+    """aqz_ds_run_device_volume_chunked: a Z/Y/X chunk shape per level, the
+    batch `first` planes into the stack, 2-5 levels.  Every lattice byte: tile
+    bytes at the oracle's places, poison wherever no plane of the batch owns
+    the byte."""
+    c = vc.fuzz_chunked_params(case)
+    dtype, geo, shapes = c["dtype"], c["geo"], c["shapes"]
+    frames = vc.fuzz_frames(c, [None] + [s[2] for s in shapes[1:]])
+    lat = vc.Lattice(oracle, geo, shapes, dtype, c["method"], frames, c["first"],
+                  with_flags=c["flags"], in_off=c["in_off"])
+    ctx = (f"case {case}: {np.dtype(dtype).name} m{c['method']} {c['w']}x{c['h']}x{c['planes']} "
+           f"x{c['stacks']} L{c['levels']} chunks {shapes[1:]} first {c['first']} in+{c['in_off']}")
+    ds = aqz.Downsampler(geo, dtype, c["method"])
+    counts = lat.run(ds, launch_stream())
+    torch_cuda().cuda.synchronize()
+    assert ds.last_batch_kind() == 5, ctx
+    assert counts == [c["n"] >> L for L in range(len(geo))], ctx
+    lat.check(oracle, ctx)
     ds.close()

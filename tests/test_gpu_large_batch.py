@@ -20,7 +20,11 @@ frames run past 2^32 bytes, and for u8 and u16 past 2^32 and 2^31 elements:
   in the log), its thread index running over more than 2^32 level-1 outputs;
 * chunk-tiled batches with zero-scan flags, tag 0 leaving whole zero tiles,
   and one chunk lattice whose level-1 capacity passes 2^32 bytes, its frame
-  offsets from the oracle's addressing.
+  offsets from the oracle's addressing;
+* the same two forms from the fused volume kernel (kind 5, family=volume_tiled
+  in the log): row overhang and column zero-fill shapes past 2^32 input bytes,
+  64 x 64 tiles whose level-1 output passes 2^32 bytes, and a Z/Y/X chunk
+  lattice whose level-1 capacity does.
 
 The batch is built on the device (frame k = base + k mod M), the library runs
 once, and level L's frame k must equal E[L] + k mod M in bits, E from one
@@ -141,3 +145,27 @@ def test_chunk_lattice_batch(cid):
     tiled = [r for r in rec["launches"] if r.get("family") == "tiled"]
     assert tiled and tiled[0]["units"] % lb.frames_for(case) == 0
     assert tiled[0]["dtype"] == lb.bpp(case)
+
+
+def check_volume_tiled(rec, case):
+    """Kind 5 from the tiled volume kernel: family=volume_tiled in the log,
+    zero-fill waves (every shape here has padding the units do not reach), and
+    units in whole plane groups."""
+    assert rec["kind"] == case.kind == 5
+    groups = lb.frames_for(case) // lb.group_planes(case)
+    runs = [r for r in rec["launches"] if r.get("family") == "volume_tiled"]
+    assert len(runs) == 1 and len(rec["launches"]) == 1, rec["launches"]
+    r = runs[0]
+    assert r["dtype"] == lb.bpp(case) and r["method"] == case.method
+    assert r["zwaves"] > 0 and r["zitems"] > 0
+    assert r["units"] % groups == 0 and r["units"] // groups == r["units_x"] * r["units_y"]
+
+
+@pytest.mark.parametrize("cid", _ids(lb.select("volume_tiled")))
+def test_volume_tiled_batch(cid):
+    check_volume_tiled(lb.record_of("volume_tiled", cid), lb.BY_ID[cid])
+
+
+@pytest.mark.parametrize("cid", _ids(lb.select("volume_lattice")))
+def test_volume_lattice_batch(cid):
+    check_volume_tiled(lb.record_of("volume_tiled", cid), lb.BY_ID[cid])

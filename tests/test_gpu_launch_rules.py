@@ -3,7 +3,8 @@ scheme each fixed geometry takes under the default launch.
 
 The library ships many kernel instantiations the default launch never
 reaches, selected by the $AQZ_* switches that launch_cascade,
-launch_cascade_tiled and launch_volume (planned in csrc/ds_plan.cpp) and the blosc
+launch_cascade_tiled, launch_volume and launch_volume_tiled (planned in
+csrc/ds_plan.cpp) and the blosc
 filter dispatch (csrc/codec_kernels.hip) read.  Each is one default flip away
 from being the product, so each rule of RULES below runs its family's case
 list (tests/launch_rule_child.py: the smallest shapes at which each store
@@ -35,6 +36,7 @@ import sys
 
 import pytest
 
+import volume_tiled_cases as vc
 from test_gpu_divergent import ROUND5_LAUNCH
 
 pytestmark = pytest.mark.gpu
@@ -63,6 +65,8 @@ U16_TILED_SPLIT = ["1500x90_uint16_64x128/m1"]  # 3000-B rows split 128-B lines,
 U8_TILED_OVERHANG = ["600x40_uint8_256x1024/m1"]  # 2560 overhang rows
 VOL_U16_DEC = ["3d_fused/uint16/m0"]         # 64 units, Decimate
 VOL_U16_MEAN = ["3d_fused/uint16/m1"]
+U8_VOLUME_TILED = vc.ZROWS_CASE_IDS[:1]     # 1030 x 37 u8, 8 x 64: rows past cov_h to zero
+U16_VOLUME_TILED = vc.ZROWS_CASE_IDS[1:]    # 512 x 8 u16, 2 x 384: columns past cov_w to zero
 U16_BITSHUFFLE = ["ts2_bs65536_n131072x4/bitshuffle"]
 U8_BITSHUFFLE = ["ts1_bs4096_n20480x2/bitshuffle"]
 
@@ -134,6 +138,12 @@ RULES = [
     rule("volume", {"AQZ_VOLUME_ZFAST": "0"},
          ({"zfast": 0}, ["3d_fused_many_groups/uint16/m0"])),
     rule("volume", {"AQZ_VOLUME_ZFAST": "1"}, ({"zfast": 1}, VOL_U16_DEC)),
+    # ---- chunk-tiled volume (plan_volume_tiled): the zwaves of
+    # volume_tiled_cases.ZROWS_PINS, worked by hand there
+    rule("volume_tiled", {"AQZ_TILED_ZROWS_PER_WAVE": "0"},
+         (vc.ZROWS_PINS[0][0], U8_VOLUME_TILED), (vc.ZROWS_PINS[0][1], U16_VOLUME_TILED)),
+    rule("volume_tiled", {"AQZ_TILED_ZROWS_PER_WAVE": "1"},
+         (vc.ZROWS_PINS[1][0], U8_VOLUME_TILED), (vc.ZROWS_PINS[1][1], U16_VOLUME_TILED)),
     # ---- blosc bit shuffle (filter_run)
     rule("codec", {"AQZ_BITSHUFFLE_WAVES": "1"}, ({"form": "vec", "waves": 1}, U16_BITSHUFFLE)),
     rule("codec", {"AQZ_BITSHUFFLE_WAVES": "2"}, ({"form": "vec", "waves": 2}, U16_BITSHUFFLE)),
@@ -215,6 +225,12 @@ DEFAULT_PINS = {
         ({"zwaves": 64, "seg_w": 0, "nt": 0}, U16_TILED_SPLIT),
         # 1-byte types: at most 32 overhang rows per zero-fill wave
         ({"zwaves": 80}, U8_TILED_OVERHANG),
+    ],
+    "volume_tiled": [
+        # 1-byte types: 32 rows per wave, ceil(112 / 32) = 4 waves, so the 64
+        # every launch has; the u16 case: the byte rule alone
+        (vc.ZROWS_PINS[None][0], U8_VOLUME_TILED),
+        (vc.ZROWS_PINS[None][1], U16_VOLUME_TILED),
     ],
     "codec": [
         ({"family": "bitshuffle", "form": "vec", "waves": 4}, U16_BITSHUFFLE),

@@ -23,50 +23,9 @@ from gpu_util import (assert_parity, empty_device, from_device, launch_stream, r
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-POISON = vc.POISON
+POISON, GUARD = vc.POISON, vc.GUARD
+Outputs, Lattice, offset_input = vc.Outputs, vc.Lattice, vc.offset_input
 MEAN = 1
-
-
-class Outputs:
-    """Poisoned tile and flag buffers of one batch of `n` level-0 planes."""
-
-    def __init__(self, geo, dtype, tiles, n, with_flags=True):
-        bpp = np.dtype(dtype).itemsize
-        self.geo, self.dtype, self.tiles, self.n = geo, dtype, tiles, n
-        self.nt = [None] + [vc.n_tiles(geo, L, tiles[L]) for L in range(1, len(geo))]
-        self.outs = [None] + [empty_device((n >> L) * self.nt[L] * tiles[L][0] * tiles[L][1] * bpp)
-                              for L in range(1, len(geo))]
-        self.flags = [None] + [empty_device((n >> L) * self.nt[L]) if with_flags else None
-                               for L in range(1, len(geo))]
-        self.poison()
-
-    def poison(self):
-        for b in self.outs[1:] + self.flags[1:]:
-            if b is not None:
-                b.fill_(POISON)
-
-    def run(self, ds, d_in, stream=None):
-        flags = None
-        if self.flags[1] is not None:
-            flags = [0] + [f.data_ptr() for f in self.flags[1:]]
-        return ds.run_device_volume_tiled(
-            d_in.data_ptr(), self.n, self.tiles, [0] + [o.data_ptr() for o in self.outs[1:]],
-            flags, launch_stream() if stream is None else stream)
-
-    def check(self, want, ctx):
-        for L in range(1, len(self.geo)):
-            tr, tc = self.tiles[L]
-            want_t, want_nz = want[L]
-            got = from_device(self.outs[L], self.dtype, (self.n >> L, self.nt[L], tr, tc))
-            assert_parity(got, want_t, f"{ctx} L{L} tiles")
-            if np.dtype(self.dtype).kind == "f":  # equal bits on every non-NaN value
-                ib = np.dtype(f"u{np.dtype(self.dtype).itemsize}")
-                ok = ~np.isnan(want_t)
-                assert np.array_equal(got.view(ib)[ok], want_t.view(ib)[ok]), f"{ctx} L{L} bits"
-            if self.flags[L] is not None:
-                raw = from_device(self.flags[L], np.uint8, (self.n >> L, self.nt[L]))
-                assert np.isin(raw, (0, 1)).all(), f"{ctx} L{L}: a flag byte was left unwritten"
-                assert np.array_equal(raw.astype(bool), want_nz), f"{ctx} L{L} zero scan"
 
 
 _WANT = {}
@@ -107,8 +66,54 @@ def test_volume_tiled_matches_oracle(aqz, oracle, case):
     ds.close()
 
 
-@pytest.mark.parametrize("dtype", [np.uint8, np.int16, np.uint32, np.int64, np.float32,
-                                   np.float64], ids=lambda d: np.dtype(d).name)
+def run_case(aqz, oracle, case, method, in_off=0, offs=None):
+    """A table case through the call: every tile byte, flag and guard."""
+    dtype = case[4]
+    geo, frames, tiles, _, want = case_setup(oracle, case, method)
+    n = len(frames)
+    ds = aqz.Downsampler(geo, dtype, method)
+    out = Outputs(geo, dtype, tiles, n, offs=offs)
+    d_in, src = offset_input(frames, in_off)
+    counts = out.run(ds, src)
+    torch_cuda().cuda.synchronize()
+    assert ds.last_batch_kind() == 5
+    assert counts == [n >> L for L in range(len(geo))]
+    out.check(want, f"{vc.case_id(case)} m{method} in+{in_off} out+{offs}")
+    raw = from_device(d_in, np.uint8, (-1,))
+    assert (raw[-GUARD:] == POISON).all() and (raw[:in_off * frames.dtype.itemsize] == POISON).all()
+    ds.close()
+    return want
+
+
+BRANCH_RUNS = [(c, m) for c, methods, _ in vc.BRANCH_CASES for m in methods]
+
+
+@pytest.mark.parametrize("case,method", BRANCH_RUNS,
+                         ids=[f"{vc.case_id(c)}-m{m}" for c, m in BRANCH_RUNS])
+def test_volume_tiled_branch_cases(aqz, oracle, case, method):
+    """The shapes of volume_tiled_cases.BRANCH_CASES: column zero-fill at one
+    level and at both, lane columns across tile edges for 1- and 2-byte types,
+    three chained runs, one tile a level, one-pixel tiles.  What each reaches
+    is asserted on the CPU (test_volume_tiled_fuzz_cases.py)."""
+    want = run_case(aqz, oracle, case, method)
+    for L in range(1, case[3]):
+        assert want[L][1].any(), f"L{L}: no nonzero tile"
+
+
+@pytest.mark.parametrize("case", vc.OFFSET_CASES, ids=vc.case_id)
+@pytest.mark.parametrize("in_off", [1, 3, 7])
+def test_volume_tiled_element_offsets(aqz, oracle, case, in_off):
+    """The input `in_off` elements past its allocation and every level's tiles
+    at an element offset of its own (1-7): the misaligned load path with its
+    last-row shift, and vector stores to odd addresses."""
+    offs = [0] + [1 + (in_off + 2 * L) % 7 for L in range(1, case[3])]
+    assert len(set(offs[1:])) == len(offs) - 1 and all(1 <= o <= 7 for o in offs[1:])
+    run_case(aqz, oracle, case, MEAN, in_off, offs)
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16, np.uint32, np.uint64, np.int8, np.int16,
+                                   np.int32, np.int64, np.float32, np.float64],
+                         ids=lambda d: np.dtype(d).name)
 @pytest.mark.parametrize("method", [0, 1, 2, 3])
 def test_volume_tiled_dtypes_methods(aqz, oracle, dtype, method):
     """Every method over the signed and float edge values (NaN, +-inf, -0.0,
@@ -162,7 +167,8 @@ def test_row_major_batch_tiles_to_the_same_bytes(aqz, oracle):
         tr, tc = tiles[L]
         planes = from_device(rows[L], dtype, (n >> L, h, w))
         tiled = np.stack([oracle.tile_frame(p, tr, tc)[0] for p in planes])
-        got = from_device(out.outs[L], dtype, tiled.shape)
+        got = from_device(out.outs[L], np.uint8, (-1,))[:tiled.nbytes].view(dtype) \
+            .reshape(tiled.shape)
         assert_parity(got, tiled, f"L{L} against the row-major batch")
     out.check(want, "no flags")  # device_tile_nonzero NULL
     ds.close()
@@ -261,6 +267,91 @@ def test_volume_chunked_places_every_tile(aqz, oracle, first):
         nz = np.stack([oracle.tile_frame(p, *vc.CHUNK_SHAPES[L][1:])[1] for p in lv[L]])
         raw = from_device(flags[L], np.uint8, nz.shape)
         assert np.isin(raw, (0, 1)).all() and np.array_equal(raw.astype(bool), nz), f"L{L} flags"
+    ds.close()
+
+
+# Five levels: runs 1-2 and 3-4 chained through the handle's scratch, level 4's
+# offsets read from the staged table by the second run.  Level 1 is 100 x 12
+# (ragged in X and Y), level 4 is 13 x 2 under one 2 x 16 tile; a batch that
+# starts at plane 16 starts level 4 in the middle of its 2-plane chunk.
+DEEP_GEO = vc.volume_geo(200, 24, 16, 5)
+DEEP_SHAPES = [None, (2, 8, 32), (2, 4, 16), (1, 2, 8), (2, 2, 16)]
+
+
+def deep_frames(dtype, seed):
+    frames = random_frames(np.random.default_rng(seed), dtype, (32, 24, 200))
+    frames[:16, :, :64] = 0  # zero tiles down to level 3
+    return frames
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.float32], ids=lambda d: np.dtype(d).name)
+@pytest.mark.parametrize("first", [0, 16], ids=lambda f: f"first{f}")
+def test_volume_chunked_chained_runs(aqz, oracle, dtype, first):
+    lat = Lattice(oracle, DEEP_GEO, DEEP_SHAPES, dtype, MEAN, deep_frames(dtype, first + 5), first)
+    if first:
+        assert lat.want[4][1][0] != 0, "level 4 starts inside its chunk"
+    for L in range(1, 5):
+        nz = np.stack([oracle.tile_frame(p, *DEEP_SHAPES[L][1:])[1] for p in lat.lv[L]])
+        assert nz.any() and (L == 4 or not nz.all()), f"L{L}: zero and nonzero tiles"
+    ds = aqz.Downsampler(DEEP_GEO, dtype, MEAN)
+    counts = lat.run(ds, launch_stream())
+    torch_cuda().cuda.synchronize()
+    assert counts == [32 >> L for L in range(5)] and ds.last_batch_kind() == 5
+    lat.check(oracle, f"{np.dtype(dtype).name} first {first}")
+    ds.close()
+
+
+# chunks three planes deep: batches that start 0, 1 and 2 planes into the last
+# level's chunk get three different offset tables
+THREE_DEEP = [(vc.CHUNK_GEO, [None, (3, 16, 16), (3, 8, 16)], 8),
+              (DEEP_GEO, [None, (3, 8, 32), (3, 4, 16), (3, 2, 8), (3, 2, 16)], 32)]
+
+
+@pytest.mark.parametrize("geo,shapes,n", THREE_DEEP, ids=["one_run", "chained"])
+def test_three_chunked_calls_queued_keep_their_own_offsets(aqz, oracle, geo, shapes, n):
+    """Three calls on one stream with nothing between them, each at its own
+    place in the stack with its own buffers, queued behind a stall
+    (stream_order.stall: a kernel that ends by itself), so that the first two
+    batches are certainly still pending when the third call stages its table.
+    The offset tables cross through two pinned halves: the third call must not
+    overwrite the half a pending batch still has to read (it waits for the
+    first, by contract).  Checked by where the bytes landed: a batch that ran
+    with another call's table puts its tiles at that call's places.  Every
+    lattice buffer has room for the largest of the three capacities, so such
+    a batch would still write inside its own buffer."""
+    from stream_order import STALL_FLOOR_MS, stall
+
+    torch = torch_cuda()
+    w, h, _ = geo[0]
+    last = len(geo) - 1
+    ds = aqz.Downsampler(geo, np.uint16, MEAN)
+
+    def batch(seed, first, room=None):
+        frames = random_frames(np.random.default_rng(seed), np.uint16, (n, h, w), specials=False)
+        return Lattice(oracle, geo, shapes, np.uint16, MEAN, frames, first, room=room)
+
+    # an unstalled call first: it grows the handle's scratch and the staging
+    # (and takes the first pinned half; the three below take the second, the
+    # first, the second)
+    warm = batch(39, 0)
+    warm.run(ds, launch_stream())
+    torch.cuda.synchronize()
+    warm.check(oracle, "unstalled call")
+    caps = [[batch(40 + i, i << last).want[L][4] for i in range(3)] for L in range(1, len(geo))]
+    room = [None] + [max(c) for c in caps]
+    lats = [batch(40 + i, i << last, room) for i in range(3)]
+    assert len({tuple(b.want[last][1]) for b in lats}) == 3, "three different offset tables"
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    done = stall(s, STALL_FLOOR_MS)
+    lats[0].run(ds, s.cuda_stream)
+    lats[1].run(ds, s.cuda_stream)
+    assert not done.query(), "the stall ended before two calls were queued: nothing was pending"
+    lats[2].run(ds, s.cuda_stream)  # may wait for the first batch
+    torch.cuda.synchronize()
+    assert ds.last_batch_kind() == 5
+    for i, b in enumerate(lats):
+        b.check(oracle, f"call {i}")
     ds.close()
 
 

@@ -31,6 +31,12 @@ def test_table_is_what_the_issue_lists():
     assert fam("row", "deep") + fam("volume", "deep") == 5
     assert [c.kind for c in lb.CASES].count(3) == 1
     assert fam("zpath") == 1 and fam("tiled") == 4 and fam("lattice") == 1
+    # tiled volumes: two shapes x (u8, u16, f32 Mean; u16 Decimate), one deep, one lattice
+    assert fam("volume_tiled", "shallow") == 2 * 4 and fam("volume_tiled", "deep") == 1
+    assert sorted((np.dtype(c.dtype).name, c.method) for c in lb.select("volume_tiled", "shallow")
+                  if c.tile == lb.COLUMN_FILL_TILE) == \
+        [("float32", 1), ("uint16", 0), ("uint16", 1), ("uint8", 1)]
+    assert fam("volume_lattice") == 1 and all(c.kind == 5 for c in lb.select("volume_tiled"))
     assert len(set(IDS)) == len(IDS)
 
 
@@ -103,6 +109,13 @@ def test_what_the_case_crosses(cid):
     if case.family == "lattice":
         assert n % lb.LATTICE_DIMS[0][2] == 0          # whole chunk layers: no byte unowned
         assert n * lb.frame_bytes(case, 1) > four      # level 1's capacity
+    if case.family == "volume_lattice":
+        for L in range(1, len(case.geo)):              # whole chunk layers at every level
+            assert (n >> L) % lb.VOLUME_LATTICE_SHAPES[L][0] == 0
+        assert (n >> 1) * lb.frame_bytes(case, 1) > four   # level 1's capacity
+    if case.family in ("volume_tiled", "volume_lattice"):
+        assert [lb.level_frames(case, L, n) for L in range(len(case.geo))] == \
+            [n >> L for L in range(len(case.geo))]
     assert lb.need_bytes(case) > n * lb.frame_bytes(case, 0)
 
 
@@ -145,7 +158,10 @@ def plan_request(case, n):
     return f"cascade {code} {case.method} {w} {h} {min(4, nl - 1)} {n}"
 
 
-@pytest.mark.parametrize("cid", IDS)
+VOLUME_TILED_IDS = [c.id for c in lb.CASES if c.family in ("volume_tiled", "volume_lattice")]
+
+
+@pytest.mark.parametrize("cid", [i for i in IDS if i not in VOLUME_TILED_IDS])
 def test_units_stay_under_the_planner_limits(ask, cid):
     """The planner (ds_plan.cpp, through plan_probe) takes each case at its
     full frame count: the plan is valid, its units are the one-frame units
@@ -178,26 +194,77 @@ def test_units_stay_under_the_planner_limits(ask, cid):
         assert n % (1 << (len(case.geo) - 1)) == 0 and n % case.geo[0][2] == 0
 
 
+@pytest.fixture(scope="module")
+def ask_volume_tiled():
+    """plan_volume_tiled through tests/cpp/volume_tiled_plan_probe.cpp."""
+    import volume_tiled_cases as vc
+    return vc.plan_probe()
+
+
+@pytest.mark.parametrize("cid", VOLUME_TILED_IDS)
+def test_volume_tiled_plans_at_full_length(ask_volume_tiled, cid):
+    """plan_volume_tiled takes each case at its full plane count: units are
+    the one-group units times the plane groups, under 2^31; the zero-fill
+    items, zitems x groups, which the kernel multiplies in 32 bits, stay under
+    2^32; every case has padding the units do not reach."""
+    import launch_rule_child as child
+    case = lb.BY_ID[cid]
+    n = lb.frames_for(case)
+    gp = lb.group_planes(case)
+    assert len(case.geo) == 3 and gp == 4 and n % gp == 0 and n < 1 << 32
+    w, h, _ = case.geo[0]
+    (r1, c1), (r2, c2) = lb.tile_of(case, 1), lb.tile_of(case, 2)
+    extra = ""
+    if case.family == "volume_lattice":
+        extra = f" stride={lb.VOLUME_LATTICE_SHAPES[1][0] * r1 * c1} flags=0"
+        assert lb.VOLUME_LATTICE_SHAPES[1][0] * r1 * c1 >= lb.VOLUME_LATTICE_SHAPES[2][0] * r2 * c2
+    req = (f"{DTYPE_CODE[np.dtype(case.dtype).name]} {case.method} {w} {h} 2 {{}} "
+           f"tile={r1}x{c1} tile2={r2}x{c2}{extra}")
+    one, full = ask_volume_tiled([req.format(gp), req.format(n)])
+    assert one is not None and full is not None, (cid, one, full)
+    groups = n // gp
+    assert full["units"] == one["units"] * groups < 1 << 31
+    assert full["zitems"] == one["zitems"] > 0 and full["zitems"] * groups < 1 << 32
+    assert full["zwaves"] > 0 and full["dtype"] == lb.bpp(case)
+    assert not child.check_launch(full), (child.check_launch(full), full)
+    for L in (1, 2):
+        assert full[f"pw{L}"] * full[f"ph{L}"] == lb.frame_elems(case, L)
+    if case.tile == lb.COLUMN_FILL_TILE:    # columns past cov_w, at level 2 for every dtype
+        assert full["cov_w2"] < full["pw2"] and full["zrows2"] == full["ph2"]
+        assert (full["cov_w1"] < full["pw1"]) == (lb.bpp(case) > 1)
+    else:                                   # rows past cov_h
+        assert full["cov_w1"] >= full["pw1"] and full["cov_h1"] < full["ph1"]
+    if case.depth == "deep" and case.family == "volume_tiled":
+        assert lb.frame_bytes(case, 1) == 4096 and 2 * lb.frame_bytes(case, 0) == 2 * 2880
+
+
 @pytest.mark.parametrize("cid", [c.id for c in lb.CASES if c.tile])
 def test_tiles_of_a_tagged_frame(oracle, cid):
     """tile_frame(E + t) = tile_frame(E) + t on the level's own elements and 0
     on the overhang, with every tile flagged nonzero, for every t > 0: shown
     for the tag the GPU test computes (1) against two more; tag 0 keeps whole
-    zero tiles."""
+    zero tiles.  For float32 both sides come from the same float addition, so
+    the values prove little there (that E + t is exact in float32 is
+    test_shift_rule_on_the_oracle's to show); what this still holds for floats
+    is the tiling: which elements of the padded tiles are the level's own
+    (`inside`), that the overhang stays zero, and the flags."""
     case = lb.BY_ID[cid]
     e = lb.expected_levels(oracle, case)
     m = lb.modulus(case.dtype)
     for L in range(1, len(case.geo)):
-        t0, f0 = lb.tiled_expectation(oracle, case, L, e[L][0], 0)
-        t1, f1 = lb.tiled_expectation(oracle, case, L, e[L][0], 1)
-        inside = t1 != t0
-        assert f1.all(), f"{cid} level {L}: a tile without an element of the level"
-        if L == 1 and case.family == "tiled":
-            assert (~f0).any() and f0.any(), f"{cid}: no whole zero tile under tag 0"
-        for t in (m // 2, m - 1):
-            tt, ft = lb.tiled_expectation(oracle, case, L, e[L][0], t)
-            assert np.array_equal(tt, t0 + inside.astype(case.dtype) * np.asarray(t, case.dtype))
-            assert np.array_equal(ft, f1)
+        for j in range(lb.per_group(case, L)):    # every plane a group emits at the level
+            t0, f0 = lb.tiled_expectation(oracle, case, L, e[L][j], 0)
+            t1, f1 = lb.tiled_expectation(oracle, case, L, e[L][j], 1)
+            inside = t1 != t0
+            assert f1.all(), f"{cid} level {L}: a tile without an element of the level"
+            # (one 64 x 64 or 2 x 384 tile holds more than the zero quarter)
+            if L == 1 and (case.family == "tiled" or case.tile == lb.VOLUME_TILED_TILE):
+                assert (~f0).any() and f0.any(), f"{cid}: no whole zero tile under tag 0"
+            for t in (m // 2, m - 1):
+                tt, ft = lb.tiled_expectation(oracle, case, L, e[L][j], t)
+                assert np.array_equal(tt, t0 + inside.astype(case.dtype) *
+                                      np.asarray(t, case.dtype))
+                assert np.array_equal(ft, f1)
 
 
 def test_crc_of_parts_is_the_oracles(oracle):

@@ -2,21 +2,17 @@
 aqz_ds_run_device_volume_tiled / _chunked.
 
 tests/cpp/volume_tiled_plan_probe.cpp links ds_plan.cpp alone, is built as a
-stand-alone program with the host compiler under ASan + UBSan, and prints the
+stand-alone program with the host compiler under ASan + UBSan
+(volume_tiled_cases.plan_probe), and prints the
 plan line of every fused run of the cases tests/test_gpu_volume_tiled.py runs
 on the GPU.  The expectations here are restated from the kernel's unit shape:
 a volume unit is 64 lanes x (16 / bytes per pixel) columns x 2^k rows x 2^k
 planes for a run of k <= 2 levels."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import volume_tiled_cases as vc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "acquire-zarr_amd", "csrc")
 DTYPE_CODE = {"uint8": 0, "uint16": 1, "uint32": 2, "uint64": 3, "int8": 4, "int16": 5,
               "int32": 6, "int64": 7, "float32": 8, "float64": 9}
 SWEEP = (520, 21, 4, 3, None, 6, 40, 2)  # the dtype and method sweep's shape
@@ -45,6 +41,7 @@ def case_requests():
     req = {}
     cases = list(vc.CASES) + [SWEEP[:4] + (dt,) + SWEEP[5:] for dt in
                               (np.uint8, np.int16, np.uint32, np.int64, np.float32, np.float64)]
+    cases += [c for c, _, _ in vc.BRANCH_CASES]
     for c in cases:
         for i, (w, h, k, n) in enumerate(runs(c)):
             req[f"{vc.case_id(c)}/run{i}"] = (request(c[4], w, h, k, n, (c[5], c[6])),
@@ -78,36 +75,16 @@ LIMITS = {
 }
 
 
-def parse(line):
-    if line == "invalid":
-        return None
-    rec = {}
-    for kv in line.split():
-        k, _, v = kv.partition("=")
-        rec[k] = int(v) if v.lstrip("-").isdigit() else v
-    return rec
-
-
 @pytest.fixture(scope="module")
-def plans(tmp_path_factory):
-    out = tmp_path_factory.mktemp("volume_tiled_plan_probe")
-    exe = str(out / "volume_tiled_plan_probe")
-    subprocess.run([os.environ.get("CXX", "g++"), "-std=c++20", "-O1", "-g",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I" + CSRC, os.path.join(ROOT, "tests", "cpp", "volume_tiled_plan_probe.cpp"),
-                    os.path.join(CSRC, "ds_plan.cpp"), "-o", exe], check=True)
-    requests = sorted({r for r, _ in REQ.values()} | {r for r, _ in LIMITS.values()})
-    env = {k: v for k, v in os.environ.items() if not k.startswith("AQZ_")}
-    r = subprocess.run([exe], input="\n".join(requests) + "\n", env=env, capture_output=True,
-                       text=True, timeout=120)
-    assert r.returncode == 0, r.stderr[-3000:]
-    lines = r.stdout.splitlines()
-    assert len(lines) == len(requests)
-    return {q: parse(l) for q, l in zip(requests, lines)}
+def plans():
+    requests = sorted({r for r, _ in REQ.values()} | {r for r, _ in LIMITS.values()} |
+                      set(zero_fill_rule_requests().values()))
+    return dict(zip(requests, vc.plan_probe()(requests)))
 
 
 def test_every_run_of_the_gpu_cases_is_planned(plans):
-    assert len(REQ) == 5 + 2 + 2 + 6  # five single runs, 2 + 1, 2 + 2, the sweep
+    # five single runs, 2 + 1, 2 + 2, the sweep; the branch table's seven single runs and 3
+    assert len(REQ) == 5 + 2 + 2 + 6 + 7 + 3
     for cid, (req, (bpp, w, h, k, n, tr, tc)) in REQ.items():
         rec = plans[req]
         assert rec is not None, f"{cid}: invalid"
@@ -165,6 +142,43 @@ def test_zero_fill_and_units_cover_the_padding_exactly_once(plans):
                 count[row, (0 if row >= ch else cw):] += 1
             assert (count == 1).all(), f"{cid} level {L}: {np.argwhere(count != 1)[:4]}"
             assert rec[f"zrows{L}"] * pw >= pw * ph - cw * ch  # whole rows at the most
+
+
+def zero_fill_rule_requests():
+    """The launch-rule child's two cases under $AQZ_TILED_ZROWS_PER_WAVE unset,
+    0 and 1."""
+    req = {}
+    for c in vc.ZROWS_CASES:
+        (w, h, k, n), = runs(c)
+        for zi in (None, 0, 1):
+            req[(vc.case_id(c), zi)] = request(c[4], w, h, k, n, (c[5], c[6]),
+                                               "" if zi is None else f"zi={zi}")
+    return req
+
+
+def test_branch_cases_zero_fill_as_their_table_says(plans):
+    """The planner's own zrows on the column zero-fill shapes: every padded
+    row where cov_w < pw, none where the units cover the level."""
+    both = plans[REQ[vc.case_id(vc.BRANCH_CASES[0][0]) + "/run0"][0]]
+    assert (both["cov_w1"], both["pw1"], both["zrows1"], both["ph1"]) == (256, 384, 4, 4)
+    assert (both["cov_w2"], both["pw2"], both["zrows2"], both["ph2"]) == (128, 384, 2, 2)
+    assert both["units"] == 4 and both["zitems"] == 4 * 2 + 2
+    second = plans[REQ[vc.case_id(vc.BRANCH_CASES[1][0]) + "/run0"][0]]
+    assert second["zrows1"] == 0 and second["cov_w1"] >= second["pw1"]
+    assert (second["cov_w2"], second["pw2"], second["zrows2"]) == (128, 200, second["ph2"])
+    deep = [plans[REQ[vc.case_id(vc.BRANCH_CASES[5][0]) + f"/run{i}"][0]] for i in range(3)]
+    assert [d["n_out"] for d in deep] == [2, 2, 2]
+
+
+def test_zero_fill_switch_pins_hold_on_the_plan(plans):
+    """The zwaves tests/test_gpu_launch_rules.py pins for the volume_tiled
+    family (volume_tiled_cases.ZROWS_PINS), on the planner's own output."""
+    req = zero_fill_rule_requests()
+    assert sorted(vc.ZROWS_PINS, key=str) == [0, 1, None]
+    for zi, pins in vc.ZROWS_PINS.items():
+        for c, fields in zip(vc.ZROWS_CASES, pins):
+            rec = plans[req[(vc.case_id(c), zi)]]
+            assert all(rec.get(k) == v for k, v in fields.items()), (zi, c, fields, rec)
 
 
 @pytest.mark.parametrize("name", list(LIMITS))
