@@ -44,6 +44,8 @@ EXPORTS = (
     "aqz_tile_frame_device_sliced",
     "aqz_ds_run_device_batch_chunked", "aqz_chunk_frame_offsets",
     "aqz_ds_run_device_volume_tiled", "aqz_ds_run_device_volume_chunked",
+    "aqz_ds_run_device_batch_tiled_base", "aqz_ds_run_device_batch_chunked_base",
+    "aqz_ds_tiled_base_flag_slots",
     "aqz_blosc_blocksize", "aqz_blosc_frame_from_filtered", "aqz_blosc_ctx_create",
     "aqz_blosc_ctx_destroy", "aqz_blosc_compress_device", "aqz_blosc_codec_info",
     "aqz_blosc_lz4_frames_device", "aqz_blosc_lz4_compress_device",
@@ -193,6 +195,11 @@ def lib() -> ctypes.CDLL:
                                                   ctypes.POINTER(vp), ctypes.POINTER(u32), vp]
     L.aqz_ds_run_device_volume_tiled.argtypes = L.aqz_ds_run_device_batch_tiled.argtypes
     L.aqz_ds_run_device_volume_chunked.argtypes = L.aqz_ds_run_device_batch_chunked.argtypes
+    L.aqz_ds_run_device_batch_tiled_base.argtypes = L.aqz_ds_run_device_batch_tiled.argtypes
+    L.aqz_ds_run_device_batch_chunked_base.argtypes = \
+        L.aqz_ds_run_device_batch_chunked.argtypes
+    L.aqz_ds_tiled_base_flag_slots.argtypes = [vp, u32, u32]
+    L.aqz_ds_tiled_base_flag_slots.restype = u32
     L.aqz_chunk_frame_offsets.argtypes = [ctypes.POINTER(Dimension), u32, u32, ctypes.c_uint64,
                                           u32, ctypes.POINTER(ctypes.c_uint64),
                                           ctypes.POINTER(ctypes.c_uint64),
@@ -597,6 +604,52 @@ class Downsampler:
             self._h, device_frames, n_frames, arr, nz, counts,
             ctypes.c_void_p(stream) if stream else None))
         return list(counts)
+
+    def run_device_batch_tiled_base(self, device_frames: int, n_frames: int, tiles,
+                                    device_outs, device_nonzero=None, stream: int = 0):
+        """run_device_batch_tiled with level 0 written as chunk tiles by the
+        same kernel: index 0 of `tiles`, `device_outs` and `device_nonzero`
+        is level 0's (tiled_base_flag_slots(...) flag bytes per tile).
+        Returns frames emitted per level."""
+        n = self.n_levels
+        tr = (ctypes.c_uint32 * n)(*[int(t[0]) if t else 0 for t in tiles])
+        tc = (ctypes.c_uint32 * n)(*[int(t[1]) if t else 0 for t in tiles])
+        outs = (ctypes.c_void_p * n)(*[int(p) if p else 0 for p in device_outs])
+        nz = None
+        if device_nonzero is not None:
+            nz = (ctypes.c_void_p * n)(*[int(p) if p else 0 for p in device_nonzero])
+        counts = (ctypes.c_uint32 * n)()
+        self._check(lib().aqz_ds_run_device_batch_tiled_base(
+            self._h, device_frames, n_frames, tr, tc, outs, nz, counts,
+            ctypes.c_void_p(stream) if stream else None))
+        return list(counts)
+
+    def run_device_batch_chunked_base(self, device_frames: int, n_frames: int, lattices,
+                                      device_nonzero=None, stream: int = 0):
+        """aqz_ds_run_device_batch_chunked_base: `lattices[L]` as for
+        run_device_batch_chunked, index 0 included (level 0's lattice, its
+        offsets from chunk_frame_offsets on level 0's own dimensions)."""
+        n = self.n_levels
+        arr = (ChunkLattice * n)()
+        keep = []
+        for L in range(n):
+            base, cap, tr, tc, stride, offs = lattices[L]
+            o = (ctypes.c_uint64 * max(n_frames, 1))(*offs)
+            keep.append(o)
+            arr[L] = ChunkLattice(int(base) if base else 0, cap, tr, tc, stride, o)
+        nz = None
+        if device_nonzero is not None:
+            nz = (ctypes.c_void_p * n)(*[int(p) if p else 0 for p in device_nonzero])
+        counts = (ctypes.c_uint32 * n)()
+        self._check(lib().aqz_ds_run_device_batch_chunked_base(
+            self._h, device_frames, n_frames, arr, nz, counts,
+            ctypes.c_void_p(stream) if stream else None))
+        return list(counts)
+
+    def tiled_base_flag_slots(self, tile_rows: int, tile_cols: int) -> int:
+        """Zero-scan flag bytes per tile of run_device_batch_tiled_base at
+        level 0 (0: bad shape)."""
+        return lib().aqz_ds_tiled_base_flag_slots(self._h, tile_rows, tile_cols)
 
     def run_device_volume_tiled(self, device_frames: int, n_frames: int, tiles,
                                 device_outs, device_nonzero=None, stream: int = 0):

@@ -48,7 +48,7 @@ AQZ_DECLARE_SHARDS(run_cascade,
                     const LevelOut*, hipStream_t))
 AQZ_DECLARE_SHARDS(run_cascade_tiled,
                    (const TiledPlan&, const void*, uint64_t, uint32_t, uint32_t, const LevelOut*,
-                    const TiledOut*, hipStream_t))
+                    const TiledOut*, const TiledOut*, hipStream_t))
 AQZ_DECLARE_SHARDS(run_volume,
                    (const VolumePlan&, const void*, uint64_t, uint32_t, uint32_t,
                     const LevelOut*, hipStream_t))
@@ -97,15 +97,16 @@ launch_cascade(int dtype, int method, const void* src, uint64_t src_frame_elems,
 hipError_t
 launch_cascade_tiled(int dtype, int method, const void* src, uint64_t src_frame_elems,
                      uint32_t W, uint32_t H, const LevelOut* outs, const TiledOut* touts,
-                     int n_out, uint32_t n_frames, hipStream_t stream)
+                     int n_out, uint32_t n_frames, hipStream_t stream, const TiledOut* tbase)
 {
     const TiledPlan pl = plan_cascade_tiled(dtype, method, src, src_frame_elems, W, H, outs,
-                                            touts, n_out, n_frames, launch_switches());
+                                            touts, n_out, n_frames, launch_switches(), tbase);
     if (!pl.valid)
         return hipErrorInvalidValue;
     if (launch_log_on())
         launch_log_record("%s", format_plan(pl).c_str());
-    AQZ_ROUTE(run_cascade_tiled, dtype, (pl, src, src_frame_elems, W, H, outs, touts, stream));
+    AQZ_ROUTE(run_cascade_tiled, dtype,
+              (pl, src, src_frame_elems, W, H, outs, touts, tbase, stream));
 }
 
 hipError_t

@@ -33,10 +33,14 @@ hipError_t launch_cascade(int dtype, int method, const void* src, uint64_t src_f
 // outs[i] gives level i's geometry; its ptr, when non-null, also receives the
 // level row-major (the input of a following launch).  Same geometry rules as
 // launch_cascade.
+// `tbase`, when non-null: the input level itself (W x H) goes out the same
+// way from the same kernel — the block each wave has loaded, stored as tiles
+// before the first reduction — with its own tile shape, flags and lattice.
 hipError_t launch_cascade_tiled(int dtype, int method, const void* src,
                                 uint64_t src_frame_elems, uint32_t W, uint32_t H,
                                 const LevelOut* outs, const TiledOut* touts, int n_out,
-                                uint32_t n_frames, hipStream_t stream);
+                                uint32_t n_frames, hipStream_t stream,
+                                const TiledOut* tbase = nullptr);
 
 // Fused 2x2x2 (XY reduce, then Z pair) over `n_planes` consecutive planes for
 // pyramids whose levels all halve both XY and Z; n_planes must be a multiple

@@ -287,8 +287,14 @@ __device__ __forceinline__ void
 store_vec(T* dst, const T (&v)[N])
 {
     constexpr int B = int(sizeof(T)) * N;
-    static_assert(B == 1 || B == 2 || B == 4 || B == 8 || B == 16, "width");
-    if constexpr (B == 16) {
+    static_assert(B == 1 || B == 2 || B == 4 || B == 8 || B == 16 || B == 32, "width");
+    if constexpr (B == 32) {
+        // a lane's whole 32-byte load (the tiled base store): two accesses
+        T half[2][N / 2];
+        __builtin_memcpy(half, v, 32);
+        store_vec<T, N / 2, NT>(dst, half[0]);
+        store_vec<T, N / 2, NT>(dst + N / 2, half[1]);
+    } else if constexpr (B == 16) {
         u32x4 q;
         __builtin_memcpy(&q, v, 16);
         u32x4_u* d = reinterpret_cast<u32x4_u*>(dst); // typedef keeps align 1
@@ -599,6 +605,16 @@ struct CascadeParams
     uint32_t band_last;              // K > 0: the band's last K waves to finish store it (no barrier)
     uint32_t seg_rowwise;            // 1: band segments of misaligned rows (StageCtx::rowb)
     uint32_t upw;                    // units per wave (cascade_kernel, columns-fastest order)
+};
+
+// cascade_base_kernel (launch_cascade_tiled with a base): the input level goes
+// out chunk-tiled as well, as tl0 (its size is W x H).  A kernel argument of
+// its own beside CascadeParams, so that every other kernel keeps its
+// arguments, and the levels' code its parameter block, as they are.
+struct BaseLevel
+{
+    TiledLevel tl0;
+    FastDiv zdiv0; // by tl0.zrows (zero_fill_base); zitems counts the levels alone
 };
 
 // Columns of T per lane in the fused cascade: 16 bytes for 1- and 2-byte
@@ -958,6 +974,225 @@ zero_fill_tiled(const P& p, uint32_t z, uint32_t nz, int lane, int n_out,
     }
 }
 
+// Level 0 of a run in chunk-tile order (cascade_base_kernel): the
+// lane's loaded block v[R][C] goes out as store_level_tiled writes a level,
+// with the block 2^NL rows by 64 * C columns and a lane store the lane's
+// whole load — same layout, same zeros past the level inside the padded
+// area, nothing past it, same flags (BaseLevel::tl0).  On edge units a lane's
+// columns past the row end hold the next row's (or frame's) bytes and rows
+// past the frame a shifted or skipped load: both are masked to zero here,
+// on the packed words as loaded (a byte mask per lane, a uniform test per
+// row), so that 1- and 2-byte pixels are never unpacked.  A function of its
+// own, so that the levels' store keeps its code in every other kernel.
+//
+// A lane's row as 32-bit words, zero past the frame: `mask` the lane's bytes
+// inside the row, `in` (uniform) the row inside the frame.
+template<typename T, int C, bool EDGE>
+__device__ __forceinline__ void
+base_row_words(const T (&row)[C], const uint32_t (&mask)[C * int(sizeof(T)) / 4], bool in,
+               uint32_t (&wd)[C * int(sizeof(T)) / 4])
+{
+    __builtin_memcpy(wd, row, C * sizeof(T));
+    if constexpr (EDGE) {
+#pragma unroll
+        for (int i = 0; i < C * int(sizeof(T)) / 4; ++i)
+            wd[i] = in ? (wd[i] & mask[i]) : 0u;
+    }
+}
+
+template<typename T, int C>
+__device__ __forceinline__ void
+base_store_row(T* d, const uint32_t (&wd)[C * int(sizeof(T)) / 4])
+{
+    T x[C];
+    __builtin_memcpy(x, wd, C * sizeof(T));
+    store_vec<T, C, true>(d, x);
+}
+
+// `t0`: BaseLevel::tl0; w x h: the frame.
+template<typename T, int C, int R, bool EDGE, int MODE>
+__device__ __forceinline__ void
+store_base_tiled(const TiledLevel& t0,
+                 uint32_t w,
+                 uint32_t h,
+                 const T (&v)[R][C],
+                 uint32_t f,
+                 uint32_t wc0,
+                 uint32_t row0,
+                 int lane)
+{
+    constexpr int RB = C * int(sizeof(T)); // a lane's bytes per row
+    constexpr int NW = RB / 4;
+    static_assert(RB == 8 || RB == 16 || RB == 32, "a lane's load");
+    const TiledLevel t = t0; // one kernarg block load
+    const uint32_t tr = t.tr, tc = t.tc;
+    const uint32_t pw = t.pw, ph = t.ph;
+    const uint32_t lc = uint32_t(lane) * C; // lane's column offset in the block
+    const uint32_t cout0 = wc0 + lc;
+    const uint64_t tile_elems = t.tstride;
+    T* base = reinterpret_cast<T*>(t.tdst) + tiled_frame_base(t, f);
+    uint8_t* flags = t.flags ? t.flags + uint64_t(f) * t.flags_frame : nullptr;
+    // the lane's bytes inside the frame, as a mask per 32-bit word of its row
+    uint32_t mask[NW] = {};
+    if constexpr (EDGE) {
+        const uint32_t nvb =
+          (cout0 < w ? min(w - cout0, uint32_t(C)) : 0u) * uint32_t(sizeof(T));
+#pragma unroll
+        for (int i = 0; i < NW; ++i) {
+            const uint32_t lo = 4u * uint32_t(i);
+            mask[i] = nvb >= lo + 4u ? ~0u : nvb <= lo ? 0u : (1u << (8u * ((nvb - lo) & 3u))) - 1u;
+        }
+    }
+    if (MODE == 1 || t.slots) {
+        const uint32_t K = t.slots;
+        // as store_level_tiled's nested form, at J = 0
+        constexpr uint32_t BW = 64u * C;
+        if (row0 >= ph || wc0 >= pw)
+            return; // past the padding (uniform): no tile, no slot
+        const uint32_t ty = t.dr.div(row0), tx0 = t.dc.div(wc0);
+        const uint32_t ry0 = row0 - ty * tr, bx = wc0 - tx0 * tc;
+        const uint32_t ltx = BW > tc ? t.dc.div(lc) : 0u; // lane's tile within the block
+        const uint32_t cx = bx + lc - ltx * tc;
+        T* tile = base + (uint64_t(ty) * t.ntx + tx0 + ltx) * tile_elems;
+        const bool act = cout0 < pw; // a block spanning tiles may pass the padding
+        // the vote and the flag store ahead of the data stores
+        // (the mask is the same for every row, so the vote ORs the rows'
+        // words as loaded — rows inside the frame only — and masks the sum:
+        // no masked copy of the block exists beside the block itself)
+        uint32_t acc[NW] = {};
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            uint32_t wd[NW];
+            __builtin_memcpy(wd, v[r], RB);
+            const bool in = !EDGE || row0 + uint32_t(r) < h; // uniform
+#pragma unroll
+            for (int i = 0; i < NW; ++i)
+                acc[i] |= in ? wd[i] : 0u;
+        }
+        uint32_t any = 0;
+#pragma unroll
+        for (int i = 0; i < NW; ++i)
+            any |= EDGE ? (acc[i] & mask[i]) : acc[i];
+        const uint64_t votes = __ballot(act && any != 0); // every lane reaches the vote
+        if (flags && lane == 0) {
+            const uint32_t srow = (ry0 / uint32_t(R)) * t.slots_x;
+            uint8_t* f0 = flags + (uint64_t(ty) * t.ntx + tx0) * K + srow;
+            if (BW <= tc) {
+                f0[bx / BW] = votes != 0 ? 1 : 0;
+            } else {
+                const uint32_t lanes = tc / C; // lanes per tile (<= 64)
+                const uint64_t m = lanes >= 64 ? ~0ull : ((1ull << lanes) - 1);
+                for (uint32_t q = 0; q * lanes < 64 && tx0 + q < t.ntx; ++q)
+                    f0[uint64_t(q) * K] = ((votes >> (q * lanes)) & m) != 0 ? 1 : 0;
+            }
+        }
+        if (act) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                uint32_t wd[NW];
+                base_row_words<T, C, EDGE>(v[r], mask, row0 + uint32_t(r) < h, wd);
+                base_store_row<T, C>(tile + uint64_t(ry0 + r) * tc + cx, wd);
+            }
+        }
+    } else if constexpr (MODE != 1) {
+        // per-row tile coordinates, per-lane tile columns
+        const uint32_t tx = t.dc.div(cout0);
+        const uint32_t cx = cout0 - tx * tc;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const uint32_t row = row0 + uint32_t(r);
+            if constexpr (EDGE) {
+                if (!(row < ph && cout0 < pw))
+                    continue;
+            }
+            const uint32_t ty = t.dr.div(row);
+            T* trow = base + uint64_t(ty) * t.ntx * tile_elems + uint64_t(row - ty * tr) * tc;
+            uint32_t wd[NW];
+            base_row_words<T, C, EDGE>(v[r], mask, row < h, wd);
+            if (cx + C <= tc) {
+                uint32_t any = 0;
+#pragma unroll
+                for (int i = 0; i < NW; ++i)
+                    any |= wd[i];
+                base_store_row<T, C>(trow + tx * tile_elems + cx, wd);
+                if (any && flags)
+                    flags[ty * t.ntx + tx] = 1;
+            } else {
+                // the lane's columns cross a tile edge (tc not a multiple of C)
+                T x[C];
+                __builtin_memcpy(x, wd, RB);
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    const uint32_t col = cout0 + c;
+                    if (col >= pw)
+                        continue;
+                    const uint32_t ctx = t.dc.div(col);
+                    const T one[1] = { x[c] };
+                    store_vec<T, 1, true>(trow + ctx * tile_elems + (col - ctx * tc), one);
+                    if (flags && nonzero_bits(x[c]))
+                        flags[ty * t.ntx + ctx] = 1;
+                }
+            }
+        }
+    }
+}
+
+// zero_fill_tiled's work for level 0 of such a run: the padded base area the
+// units do not reach, per (frame, padded row) item (tl0.zrows a frame), and
+// the slot flags of blocks no wave owns.  The levels keep zero_fill_tiled.
+template<typename T>
+__device__ __forceinline__ void
+zero_fill_base(const BaseLevel& b, uint32_t z, uint32_t nz, int lane, uint32_t n_frames)
+{
+    constexpr int E = 16 / int(sizeof(T));
+    const TiledLevel t = b.tl0;
+    const uint32_t items = t.zrows * n_frames; // < 2^32: checked at launch
+    const uint32_t tr = t.tr, tc = t.tc, pw = t.pw;
+    const uint32_t cw = min(t.cov_w, pw), chh = min(t.cov_h, t.ph);
+    const uint64_t tile_elems = t.tstride;
+    for (uint32_t it = z; it < items; it += nz) {
+        const uint32_t f = b.zdiv0.div(it);
+        const uint32_t rem = it - f * t.zrows;
+        const uint32_t row = cw < pw ? rem : chh + rem;
+        const uint32_t a = row >= chh ? 0u : cw;
+        const uint32_t ty = t.dr.div(row);
+        T* trow = reinterpret_cast<T*>(t.tdst) + tiled_frame_base(t, f) +
+                  uint64_t(ty) * t.ntx * tile_elems + uint64_t(row - ty * tr) * tc;
+        for (uint32_t tx = t.dc.div(a); tx * tc < pw; ++tx) {
+            const uint32_t c0 = max(a, tx * tc) - tx * tc; // segment [c0, tc) in the tile row
+            T* seg = trow + tx * tile_elems + c0;
+            const uint32_t len = tc - c0;
+            for (uint32_t i = uint32_t(lane) * E; i < len; i += 64u * E) {
+                if (i + E <= len) {
+                    const T zeros[E] = {};
+                    store_vec<T, E, true>(seg + i, zeros);
+                } else {
+                    for (uint32_t k = i; k < len; ++k) {
+                        const T zero[1] = { T(0) };
+                        store_vec<T, 1, true>(seg + k, zero);
+                    }
+                }
+            }
+        }
+    }
+    if (!t.slots || !t.flags || (t.cov_w >= t.pw && t.cov_h >= t.ph))
+        return;
+    const uint32_t K = t.slots, kx = t.slots_x, ky = K / kx;
+    const uint32_t bh = t.tr / ky, bw = t.tc / kx; // slot size
+    const uint64_t per_frame = t.flags_frame;
+    const uint64_t total = per_frame * n_frames;
+    for (uint64_t q = uint64_t(z) * 64 + lane; q < total; q += uint64_t(nz) * 64) {
+        const uint32_t f = uint32_t(q / per_frame);
+        const uint32_t s = uint32_t(q - uint64_t(f) * per_frame);
+        const uint32_t tile = s / K, slot = s - tile * K;
+        const uint32_t ty = tile / t.ntx, tx = tile - ty * t.ntx;
+        const uint32_t r0 = ty * t.tr + (slot / kx) * bh;
+        const uint32_t c0 = tx * t.tc + (slot % kx) * bw;
+        if (r0 >= t.cov_h || c0 >= t.cov_w)
+            t.flags[q] = 0;
+    }
+}
+
 // Row-band staging (cascade_band_kernel): levels whose rows split 64-byte
 // DRAM bursts are written to LDS first, so that one workgroup — which owns
 // a whole row band of the frame — stores each level's band as one
@@ -1114,6 +1349,10 @@ cascade_level(const CascadeParams& p,
 // (F config Min/Max fetched 2.3-2.7% more than the frame).
 // The halves are two tiles of E columns per lane, reduced and stored
 // (staged) one after the other by the E-column cascade.
+//
+// TILED 3 / 4 (cascade_base_kernel, `base` set): TILED 1 / 2 with the loaded
+// block itself stored as level 0's chunk tiles first — the same bytes for
+// every method, since the store sees only the loads.
 template<typename T, int M, int NL, int C, bool NT, bool EDGE, bool NTS = true,
          int STAGED = 0, int TILED = 0, bool SPLIT = false>
 __device__ __forceinline__ void
@@ -1122,7 +1361,8 @@ cascade_unit(const CascadeParams& p,
              uint32_t row0,
              uint32_t col0,
              int lane,
-             const StageCtx* sc = nullptr)
+             const StageCtx* sc = nullptr,
+             const BaseLevel* base = nullptr)
 {
     constexpr int R = 1 << NL;
     constexpr int RB = C * int(sizeof(T));   // bytes per lane per row
@@ -1171,8 +1411,12 @@ cascade_unit(const CascadeParams& p,
     // keep every load above the reductions (the scheduler would otherwise
     // hold back the last rows' loads to save registers)
     __builtin_amdgcn_sched_barrier(0);
-    cascade_level<T, M, C, 1, NL, R, C, EDGE, NTS, STAGED, TILED>(p, v, f, row0, col0, lane,
-                                                                   sc);
+    constexpr bool kBase = TILED >= 3;
+    if constexpr (kBase)
+        store_base_tiled<T, C, R, EDGE, TILED - 2>(base->tl0, p.W, p.H, v, f,
+                                                   col0 - uint32_t(lane) * C, row0, lane);
+    cascade_level<T, M, C, 1, NL, R, C, EDGE, NTS, STAGED, kBase ? TILED - 2 : TILED>(
+      p, v, f, row0, col0, lane, sc);
 }
 
 // TILED (1: blocks and tiles nest, 2: any chunk shape): every level goes out
@@ -1290,6 +1534,65 @@ cascade_kernel(CascadeParams p)
             cascade_unit<T, M, NL, C, NT, true, true, 0, 0>(p, f, row0, col0, lane);
         }
     }
+}
+
+// cascade_kernel<..., TILED = MODE> with the input level written as chunk
+// tiles too (launch_cascade_tiled with a base; MODE 1: every level, the base
+// included, nests with the wave blocks, 2: any chunk shape).  The zero-fill
+// blocks do the base's items first, then the levels'; the cascade blocks map
+// one unit per wave as there, and each stores its loaded block as tiles
+// before it reduces it (cascade_unit TILED 3 / 4).  A kernel of its own: the
+// tiled instantiations without a base stay as they are.
+template<typename T, int M, int NL, int C, bool NT, int MODE>
+__global__ __launch_bounds__(512) void
+cascade_base_kernel(CascadeParams p, BaseLevel b)
+{
+    constexpr int R = 1 << NL;
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t blk = blockIdx.x;
+    const uint32_t wpb = blockDim.x >> 6;
+    const uint32_t zb = p.zwaves / wpb;
+    if (blk < zb) {
+        zero_fill_base<T>(b, blk * wpb + wave, p.zwaves, lane,
+                          p.total_units / (p.units_x * p.units_y));
+        zero_fill_tiled<T>(p, blk * wpb + wave, p.zwaves, lane, NL,
+                           p.total_units / (p.units_x * p.units_y));
+        return;
+    }
+    blk -= zb;
+    if (p.remap) {
+        const uint32_t nb8 = p.main_blocks & ~7u;
+        if (blk < nb8)
+            blk = (blk & 7u) * (nb8 >> 3) + (blk >> 3);
+    }
+    uint32_t ux, uy, f;
+    if (p.seg_w) {
+        const uint32_t segs = (p.units_x + p.seg_w - 1) / p.seg_w;
+        const uint32_t band = blk / segs;
+        ux = (blk - band * segs) * p.seg_w + wave;
+        if (ux >= p.units_x || band >= p.total_units / p.units_x)
+            return;
+        uy = band % p.units_y;
+        f = band / p.units_y;
+    } else {
+        const uint32_t u = blk * wpb + wave;
+        if (u >= p.total_units)
+            return;
+        ux = u % p.units_x;
+        const uint32_t t = u / p.units_x;
+        uy = t % p.units_y;
+        f = t / p.units_y;
+    }
+    const uint32_t row0 = uy * R;
+    const uint32_t tile_col0 = ux * (64u * C);
+    const uint32_t col0 = tile_col0 + uint32_t(lane) * C;
+    if ((tile_col0 + 64u * C <= p.W) && (row0 + R <= p.H))
+        cascade_unit<T, M, NL, C, NT, false, true, 0, MODE + 2>(p, f, row0, col0, lane, nullptr,
+                                                                &b);
+    else
+        cascade_unit<T, M, NL, C, NT, true, true, 0, MODE + 2>(p, f, row0, col0, lane, nullptr,
+                                                               &b);
 }
 
 // Band-staged cascade: one workgroup per row band of one frame, one wave per
@@ -2271,12 +2574,23 @@ AQZ_SHARDED(run_cascade)(const CascadePlan& pl, const void* src, uint64_t src_fr
 hipError_t
 AQZ_SHARDED(run_cascade_tiled)(const TiledPlan& pl, const void* src, uint64_t src_frame_elems,
                                uint32_t W, uint32_t H, const LevelOut* outs,
-                               const TiledOut* touts, hipStream_t stream)
+                               const TiledOut* touts, const TiledOut* tbase, hipStream_t stream)
 {
-    if (!pl.valid)
+    if (!pl.valid || pl.base != (tbase != nullptr))
         return hipErrorInvalidValue;
     CascadeParams p{};
+    BaseLevel b{};
     fill_frames(p, pl, src, src_frame_elems, W, H, outs);
+    if (pl.base) {
+        fill_tiled_level(b.tl0, pl.base_lv, *tbase);
+        b.zdiv0 = FastDiv::make(pl.base_lv.zrows ? pl.base_lv.zrows : 1);
+        if (pl.base_lv.clear_flags) {
+            const hipError_t e = hipMemsetAsync(
+              tbase->nonzero, 0, size_t(pl.n_frames) * pl.base_lv.ntx * pl.base_lv.nty, stream);
+            if (e != hipSuccess)
+                return e;
+        }
+    }
     for (int i = 0; i < pl.n_out; ++i) {
         const TiledOut& t = touts[i];
         const TiledLevelPlan& l = pl.lv[i];
@@ -2301,17 +2615,28 @@ AQZ_SHARDED(run_cascade_tiled)(const TiledPlan& pl, const void* src, uint64_t sr
         constexpr int CW = kCascadeCols<T>;
         constexpr int CN = CW / 2;
         auto go = [&](auto mtag, auto ltag, auto nttag, auto ctag, auto mdtag) -> hipError_t {
-            hipLaunchKernelGGL((cascade_kernel<T, decltype(mtag)::value, decltype(ltag)::value,
-                                               decltype(ctag)::value, decltype(nttag)::value,
-                                               decltype(mdtag)::value>),
-                               grid, block, 0, stream, p);
+            constexpr int MD = decltype(mdtag)::value;
+            if constexpr (MD >= 3)
+                hipLaunchKernelGGL(
+                  (cascade_base_kernel<T, decltype(mtag)::value, decltype(ltag)::value,
+                                       decltype(ctag)::value, decltype(nttag)::value, MD - 2>),
+                  grid, block, 0, stream, p, b);
+            else
+                hipLaunchKernelGGL(
+                  (cascade_kernel<T, decltype(mtag)::value, decltype(ltag)::value,
+                                  decltype(ctag)::value, decltype(nttag)::value, MD>),
+                  grid, block, 0, stream, p);
             return hipGetLastError();
         };
         return with_method(pl.method, [&](auto mtag) -> hipError_t {
             return with_levels(pl.n_out, [&](auto ltag) -> hipError_t {
                 return with_flag(pl.nt != 0, [&](auto nttag) -> hipError_t {
-                    // tiled mode 1: wave blocks and tiles nest; 2: they do not
+                    // tiled mode 1: wave blocks and tiles nest; 2: they do not;
+                    // 3 / 4: the same with the base level written as tiles too
                     auto go_c = [&](auto ctag) -> hipError_t {
+                        if (pl.base)
+                            return pl.nested ? go(mtag, ltag, nttag, ctag, int_tag<3>{})
+                                             : go(mtag, ltag, nttag, ctag, int_tag<4>{});
                         return pl.nested ? go(mtag, ltag, nttag, ctag, int_tag<1>{})
                                          : go(mtag, ltag, nttag, ctag, int_tag<2>{});
                     };

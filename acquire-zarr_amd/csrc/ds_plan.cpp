@@ -479,9 +479,12 @@ cascade_tiled_cols(int dtype, uint32_t W, const LaunchSwitches& sw)
     return W >= 64 * cw ? cw : cw / 2;
 }
 
+namespace {
+
+// cascade_tiled_slots for level >= 1, cascade_tiled_base_slots for level 0
 uint32_t
-cascade_tiled_slots(int dtype, uint32_t W, int n_out, int level, uint32_t tile_rows,
-                    uint32_t tile_cols, uint32_t* slots_x, const LaunchSwitches& sw)
+tiled_slots_at(int dtype, uint32_t W, int n_out, int level, uint32_t tile_rows,
+               uint32_t tile_cols, uint32_t* slots_x, const LaunchSwitches& sw)
 {
     const uint32_t cols = cascade_tiled_cols(dtype, W, sw);
     const uint32_t cw = (64u * cols) >> level;       // level columns per wave block
@@ -489,7 +492,7 @@ cascade_tiled_slots(int dtype, uint32_t W, int n_out, int level, uint32_t tile_r
     const uint32_t co = std::max(1u, cols >> level); // columns per lane store
     if (slots_x)
         *slots_x = 1;
-    if (cols == 0 || level < 1 || level > n_out || tile_rows == 0 || tile_cols == 0 ||
+    if (cols == 0 || level < 0 || level > n_out || tile_rows == 0 || tile_cols == 0 ||
         tile_rows % rh != 0)
         return 0;
     // blocks inside tiles: one slot per block; blocks spanning whole tiles
@@ -506,10 +509,31 @@ cascade_tiled_slots(int dtype, uint32_t W, int n_out, int level, uint32_t tile_r
     return (tile_rows / rh) * sx;
 }
 
+} // namespace
+
+uint32_t
+cascade_tiled_slots(int dtype, uint32_t W, int n_out, int level, uint32_t tile_rows,
+                    uint32_t tile_cols, uint32_t* slots_x, const LaunchSwitches& sw)
+{
+    if (level < 1) {
+        if (slots_x)
+            *slots_x = 1;
+        return 0;
+    }
+    return tiled_slots_at(dtype, W, n_out, level, tile_rows, tile_cols, slots_x, sw);
+}
+
+uint32_t
+cascade_tiled_base_slots(int dtype, uint32_t W, int n_out, uint32_t tile_rows,
+                         uint32_t tile_cols, uint32_t* slots_x, const LaunchSwitches& sw)
+{
+    return tiled_slots_at(dtype, W, n_out, 0, tile_rows, tile_cols, slots_x, sw);
+}
+
 TiledPlan
 plan_cascade_tiled(int dtype, int method, const void* src, uint64_t src_frame_elems, uint32_t W,
                    uint32_t H, const LevelOut* outs, const TiledOut* touts, int n_out,
-                   uint32_t n_frames, const LaunchSwitches& sw)
+                   uint32_t n_frames, const LaunchSwitches& sw, const TiledOut* tbase)
 {
     TiledPlan p;
     // the flag layout (cascade_tiled_slots) assumes the geometry-only choice;
@@ -536,48 +560,61 @@ plan_cascade_tiled(int dtype, int method, const void* src, uint64_t src_frame_el
         return p;
     p.total_units = uint32_t(total);
     bool flag_fill = false;
-    for (int i = 0; i < n_out; ++i) {
-        const TiledOut& t = touts[i];
+    uint64_t zitems_frame = 0; // p.zitems before it is known to fit 32 bits
+    // level `lvl` of the launch (0: the input itself, `tbase`), w x h
+    const auto plan_level = [&](TiledLevelPlan& q, const TiledOut& t, int lvl, uint32_t w,
+                                uint32_t h) {
         if (!t.ptr || t.tile_rows == 0 || t.tile_cols == 0 ||
             reinterpret_cast<uintptr_t>(t.ptr) % b != 0)
-            return p;
-        TiledLevelPlan& q = p.lv[i];
-        q.ntx = (outs[i].w + t.tile_cols - 1) / t.tile_cols;
-        q.nty = (outs[i].h + t.tile_rows - 1) / t.tile_rows;
+            return false;
+        q.ntx = (w + t.tile_cols - 1) / t.tile_cols;
+        q.nty = (h + t.tile_rows - 1) / t.tile_rows;
         const uint64_t pw = uint64_t(q.ntx) * t.tile_cols, ph = uint64_t(q.nty) * t.tile_rows;
         if (pw >= (1ull << 31) || ph >= (1ull << 31))
-            return p;
+            return false;
         q.tframe_elems = pw * ph;
         q.tstride = t.frame_offsets ? t.tile_stride : uint64_t(t.tile_rows) * t.tile_cols;
         if (q.tstride < uint64_t(t.tile_rows) * t.tile_cols)
-            return p;
+            return false;
         q.pw = uint32_t(pw);
         q.ph = uint32_t(ph);
-        q.cov_w = p.units_x * ((64u * cols) >> (i + 1));
-        q.cov_h = p.units_y * (R >> (i + 1));
+        // below 2^31: units_x * 64 * cols < W + 64 * cols, units_y * R < H + R
+        q.cov_w = uint32_t((uint64_t(p.units_x) * (64u * cols)) >> lvl);
+        q.cov_h = uint32_t((uint64_t(p.units_y) * R) >> lvl);
         q.zrows = q.cov_w < pw ? uint32_t(ph) : (q.cov_h < ph ? uint32_t(ph) - q.cov_h : 0u);
-        p.zitems += q.zrows;
-        q.slots = cascade_tiled_slots(dtype, W, n_out, i + 1, t.tile_rows, t.tile_cols,
-                                      &q.slots_x, sw);
+        zitems_frame += q.zrows;
+        q.slots = tiled_slots_at(dtype, W, n_out, lvl, t.tile_rows, t.tile_cols, &q.slots_x, sw);
         if (!q.slots)
             p.nested = false;
         q.flags_frame = q.ntx * q.nty * std::max<uint32_t>(1, q.slots);
         if (t.nonzero && q.slots && (q.cov_w < pw || q.cov_h < ph))
             flag_fill = true;
         q.clear_flags = t.nonzero && !q.slots;
+        return true;
+    };
+    for (int i = 0; i < n_out; ++i)
+        if (!plan_level(p.lv[i], touts[i], i + 1, outs[i].w, outs[i].h))
+            return p;
+    if (tbase) {
+        if (!plan_level(p.base_lv, *tbase, 0, W, H))
+            return p;
+        p.base = true;
     }
     // zero-fill waves: a whole number of 8-block (one per XCD) groups
-    const uint64_t zitems = uint64_t(p.zitems) * n_frames;
+    // (the kernel walks the base's items and the levels' one after the other,
+    // each count in 32 bits: the sum is held to that)
+    const uint64_t zitems = zitems_frame * n_frames;
     if (zitems >= (1ull << 32))
         return p;
+    p.zitems = uint32_t(zitems_frame) - p.base_lv.zrows; // the levels' alone
     // One zero-fill wave per 128 KiB of overhang (64..4096).  The waves run
     // first and hold their slots while the cascade blocks start; one per
     // item (up to 4096) cost 4-5% at 3000^2 and 5472x3648 against 512, and
     // putting them after the cascade blocks made them the kernel's tail
     // (profiles/r02/tiled_zero_fill_ab.log).
     uint64_t zbytes = 0;
-    for (int i = 0; i < n_out; ++i) {
-        const TiledLevelPlan& q = p.lv[i];
+    for (int i = p.base ? -1 : 0; i < n_out; ++i) {
+        const TiledLevelPlan& q = i < 0 ? p.base_lv : p.lv[i];
         const uint64_t cw = std::min(q.cov_w, q.pw), chh = std::min(q.cov_h, q.ph);
         zbytes += (uint64_t(q.pw) * q.ph - cw * chh) * b;
     }
@@ -644,11 +681,16 @@ plan_cascade_tiled(int dtype, int method, const void* src, uint64_t src_frame_el
 std::string
 format_plan(const TiledPlan& p)
 {
-    return line("family=tiled dtype=%u method=%d n_out=%d grid=%u block=%u units=%u "
-                "units_x=%u cols=%u nt=%u remap=%u seg_w=%u wpb=%u zwaves=%u nested=%d "
-                "main_blocks=%u",
-                p.bytes, p.method, p.n_out, p.grid, p.block, p.total_units, p.units_x, p.cols,
-                p.nt, p.remap, p.seg_w, p.wpb, p.zwaves, int(p.nested), p.main_blocks);
+    const std::string s =
+      line("family=tiled dtype=%u method=%d n_out=%d grid=%u block=%u units=%u "
+           "units_x=%u cols=%u nt=%u remap=%u seg_w=%u wpb=%u zwaves=%u nested=%d "
+           "main_blocks=%u",
+           p.bytes, p.method, p.n_out, p.grid, p.block, p.total_units, p.units_x, p.cols, p.nt,
+           p.remap, p.seg_w, p.wpb, p.zwaves, int(p.nested), p.main_blocks);
+    if (!p.base)
+        return s;
+    return s + line(" base=1 base_slots=%u base_slots_x=%u base_zrows=%u", p.base_lv.slots,
+                    p.base_lv.slots_x, p.base_lv.zrows);
 }
 
 bool

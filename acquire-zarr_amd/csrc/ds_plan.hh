@@ -170,6 +170,12 @@ uint32_t cascade_tiled_cols(int dtype, uint32_t W, const LaunchSwitches& sw = la
 uint32_t cascade_tiled_slots(int dtype, uint32_t W, int n_out, int level, uint32_t tile_rows,
                              uint32_t tile_cols, uint32_t* slots_x,
                              const LaunchSwitches& sw = launch_switches());
+// The same rule for the launch's input level written as tiles too
+// (plan_cascade_tiled with a base): wave blocks of 2^n_out rows x 64 * cols
+// columns, `cols` columns per lane store.
+uint32_t cascade_tiled_base_slots(int dtype, uint32_t W, int n_out, uint32_t tile_rows,
+                                  uint32_t tile_cols, uint32_t* slots_x,
+                                  const LaunchSwitches& sw = launch_switches());
 
 bool volume_supported(int dtype, const void* src, uint32_t W, uint32_t H, const LevelOut* outs,
                       int n_out);
@@ -223,6 +229,13 @@ struct TiledPlan
     uint32_t units_x = 0, units_y = 0, total_units = 0;
     uint32_t zitems = 0, zwaves = 0, main_blocks = 0, remap = 0, seg_w = 0;
     TiledLevelPlan lv[kMaxFusedLevels];
+    // The launch's input level written as tiles too (selector: TILED 3 / 4
+    // for nested / not): its units cover cov_w = units_x * 64 * cols by
+    // cov_h = units_y * 2^n_out, never less than the frame, so its zero-fill
+    // items (base_lv.zrows a frame, beside zitems for the levels) are the
+    // padded area past them alone.  zwaves, nested and the limits count it.
+    bool base = false;
+    TiledLevelPlan base_lv;
 };
 
 struct VolumePlan
@@ -263,7 +276,8 @@ CascadePlan plan_cascade(int dtype, int method, const void* src, uint64_t src_fr
                          uint32_t n_frames, uint32_t lds_cap, const LaunchSwitches& sw);
 TiledPlan plan_cascade_tiled(int dtype, int method, const void* src, uint64_t src_frame_elems,
                              uint32_t W, uint32_t H, const LevelOut* outs, const TiledOut* touts,
-                             int n_out, uint32_t n_frames, const LaunchSwitches& sw);
+                             int n_out, uint32_t n_frames, const LaunchSwitches& sw,
+                             const TiledOut* tbase = nullptr);
 VolumePlan plan_volume(int dtype, int method, const void* src, uint64_t src_frame_elems,
                        uint32_t W, uint32_t H, const LevelOut* outs, int n_out,
                        uint32_t n_planes, const LaunchSwitches& sw);

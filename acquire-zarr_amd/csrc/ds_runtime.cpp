@@ -1785,8 +1785,11 @@ namespace {
 // n_frames.
 int
 stage_lattice(aqz_ds* ds, const aqz_chunk_lattice* lat, uint32_t n_frames, hipStream_t stream,
-              std::vector<const uint64_t*>* dev, int* half_out, bool halving = false)
+              std::vector<const uint64_t*>* dev, int* half_out, bool halving = false,
+              bool base = false)
 {
+    // `base`: slot 0 (level 0's offsets) is staged too
+    const uint32_t l0 = base ? 0 : 1;
     const size_t need = size_t(ds->n) * n_frames;
     if (ds->d_lattice.capacity() < 2 * need * 8 || ds->h_lattice.capacity() < 2 * need * 8) {
         for (const aqz::Event& e : ds->lattice_done)
@@ -1807,11 +1810,11 @@ stage_lattice(aqz_ds* ds, const aqz_chunk_lattice* lat, uint32_t n_frames, hipSt
     uint64_t* h = static_cast<uint64_t*>(ds->h_lattice.get()) + size_t(half) * lattice_half;
     uint64_t* d = static_cast<uint64_t*>(ds->d_lattice.get()) + size_t(half) * lattice_half;
     dev->assign(ds->n, nullptr);
-    for (uint32_t l = 1; l < ds->n; ++l)
+    for (uint32_t l = l0; l < ds->n; ++l)
         for (uint32_t k = 0, nk = halving ? n_frames >> l : n_frames; k < nk; ++k)
             h[size_t(l) * n_frames + k] = lat[l].frame_offset_bytes[k] / ds->bpp;
     HIP_TRY(ds, hipMemcpyAsync(d, h, need * 8, hipMemcpyHostToDevice, stream), "lattice upload");
-    for (uint32_t l = 1; l < ds->n; ++l)
+    for (uint32_t l = l0; l < ds->n; ++l)
         (*dev)[l] = d + size_t(l) * n_frames;
     *half_out = half;
     return AQZ_OK;
@@ -1819,7 +1822,8 @@ stage_lattice(aqz_ds* ds, const aqz_chunk_lattice* lat, uint32_t n_frames, hipSt
 
 // aqz_ds_run_device_batch_tiled (lat == nullptr: tiles of a frame back to
 // back, frames back to back) and aqz_ds_run_device_batch_chunked (every tile
-// into its chunk of the lattice).
+// into its chunk of the lattice).  `base` (the _base forms): index 0 of the
+// per-level arguments is level 0's, written as tiles by the first run.
 int
 run_tiled(aqz_ds* ds,
           const char* who,
@@ -1831,22 +1835,28 @@ run_tiled(aqz_ds* ds,
           const aqz_chunk_lattice* lat,
           uint8_t* const* device_tile_nonzero,
           uint32_t* out_counts,
-          void* hip_stream)
+          void* hip_stream,
+          bool base = false)
 {
     const std::string w(who);
     if (int rc = settle(ds))
         return rc;
     if (ds->transpose)
-        return ds->fail_arg(w + ": input transposition applies to the per-frame path only");
+        return ds->fail_arg(w + ": input transposition applies to the per-frame path only" +
+                            (base ? " (level 0 is tiled as it arrives)" : ""));
     ds->last_input = nullptr;
     if (!device_frames || (!lat && (!device_out_levels || !tile_rows || !tile_cols)))
         return ds->fail_arg(w + ": null argument");
     if (ds->n < 2)
-        return ds->fail_arg(w + ": the pyramid has no level to tile");
-    for (uint32_t l = 1; l < ds->n; ++l) {
-        if (!ds->lv[l].xy || ds->lv[l].zh)
+        return ds->fail_arg(w + ": the pyramid has no level to tile" +
+                            (base ? ": level 0 is tiled by the kernel that reduces it" : ""));
+    // levels 1 .. n-1 in order, then (`base`) level 0
+    for (uint32_t i = 1; i < ds->n + (base ? 1u : 0u); ++i) {
+        const uint32_t l = i < ds->n ? i : 0;
+        if (l && (!ds->lv[l].xy || ds->lv[l].zh))
             return ds->fail_arg(w + ": pure-XY (2-D) pyramids only; level " + std::to_string(l) +
-                                " does not halve XY alone");
+                                " does not halve XY alone" +
+                                (base ? ", so level 0 cannot be tiled by this call either" : ""));
         const uint32_t tr = lat ? lat[l].tile_rows : tile_rows[l];
         const uint32_t tc = lat ? lat[l].tile_cols : tile_cols[l];
         const void* out = lat ? lat[l].device_base : device_out_levels[l];
@@ -1875,13 +1885,64 @@ run_tiled(aqz_ds* ds,
             }
         }
     }
+    const auto tiled_out = [&](uint32_t l,
+                               const std::vector<const uint64_t*>& off) -> aqz::TiledOut {
+        uint8_t* nz = device_tile_nonzero ? device_tile_nonzero[l] : nullptr;
+        if (lat)
+            return { lat[l].device_base, lat[l].tile_rows, lat[l].tile_cols, nz, off[l],
+                     lat[l].chunk_stride_bytes / ds->bpp };
+        return { device_out_levels[l], tile_rows[l], tile_cols[l], nz };
+    };
+    // one run's outputs: row-major nowhere (the loop below fills in the chain),
+    // level l's tiles by the caller's arguments and the staged offsets `off`
+    const auto run_outs = [&](uint32_t L, uint32_t k, const std::vector<const uint64_t*>& off,
+                              aqz::LevelOut* o, aqz::TiledOut* t) {
+        fill_outs(ds, L, k, [](uint32_t) { return nullptr; }, o);
+        for (uint32_t j = 0; j < k; ++j)
+            t[j] = tiled_out(L + j, off);
+    };
+    if (base) {
+        // every run's plan, the first with the base in it, before anything is
+        // queued: a later run refused after the first had run would leave
+        // level 0 written by a call that fails.  (The offsets' host copy
+        // stands in for the staged one, and an aligned address for the chain
+        // scratch later runs read: a plan reads neither.)
+        std::vector<const uint64_t*> host_off(ds->n, nullptr);
+        if (lat)
+            for (uint32_t l = 0; l < ds->n; ++l)
+                host_off[l] = lat[l].frame_offset_bytes;
+        const aqz::TiledOut t0 = tiled_out(0, host_off);
+        for (uint32_t L = 1; L < ds->n;) {
+            const uint32_t k = std::min<uint32_t>(ds->n - L, aqz::kMaxFusedLevels);
+            aqz::LevelOut o[aqz::kMaxFusedLevels];
+            aqz::TiledOut t[aqz::kMaxFusedLevels];
+            run_outs(L, k, host_off, o, t);
+            const void* from = L == 1 ? device_frames : reinterpret_cast<const void*>(uintptr_t(256));
+            const aqz_level_desc& a = ds->lv[L - 1].desc;
+            const std::string also = L == 1 ? "" : ", so level 0 is not written either";
+            if (!aqz::cascade_supported(ds->dtype, from, ds->lv[L - 1].elems(), a.width, a.height,
+                                        o, int(k)))
+                return ds->fail_arg(w + ": level " + std::to_string(L - 1) +
+                                    " is narrower than one vector load (" +
+                                    std::to_string(a.width) + " px) or misaligned" + also);
+            if (!aqz::plan_cascade_tiled(ds->dtype, ds->method, from, ds->lv[L - 1].elems(),
+                                         a.width, a.height, o, t, int(k), n_frames,
+                                         aqz::launch_switches(), L == 1 ? &t0 : nullptr)
+                   .valid)
+                return ds->fail_arg(w + ": level " + std::to_string(L - 1) +
+                                    ": unsupported geometry (a misaligned output, a padded side "
+                                    "of 2^31 or more, 2^30 or more units or 2^32 or more "
+                                    "zero-fill rows, or no frames)" + also);
+            L += k;
+        }
+    }
     if (int rc = bind_device(ds))
         return rc;
     hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ds->stream;
     std::vector<const uint64_t*> d_off;
     int half = -1;
     if (lat)
-        if (int rc = stage_lattice(ds, lat, n_frames, stream, &d_off, &half))
+        if (int rc = stage_lattice(ds, lat, n_frames, stream, &d_off, &half, false, base))
             return rc;
     // From here on the staged half's upload is queued on `stream`: whatever
     // the exit, record the event that guards the pinned half, so a later call
@@ -1939,16 +2000,11 @@ run_tiled(aqz_ds* ds,
         aqz::LevelOut o[aqz::kMaxFusedLevels];
         aqz::TiledOut t[aqz::kMaxFusedLevels];
         // row-major only where the run feeds the next one (below)
-        fill_outs(ds, L, k, [](uint32_t) { return nullptr; }, o);
-        for (uint32_t j = 0; j < k; ++j) {
-            const uint32_t l = L + j;
-            uint8_t* nz = device_tile_nonzero ? device_tile_nonzero[l] : nullptr;
-            if (lat)
-                t[j] = { lat[l].device_base, lat[l].tile_rows, lat[l].tile_cols, nz, d_off[l],
-                         lat[l].chunk_stride_bytes / ds->bpp };
-            else
-                t[j] = { device_out_levels[l], tile_rows[l], tile_cols[l], nz };
-        }
+        run_outs(L, k, d_off, o, t);
+        // the base leaves with the run that reads it; later runs read chain
+        // scratch and know nothing of level 0
+        const bool with_base = base && run == 0;
+        const aqz::TiledOut t0 = with_base ? tiled_out(0, d_off) : aqz::TiledOut{};
         void* chain = ds->d_chain.bytes() + (run & 1) * (ds->d_chain.capacity() / 2);
         if (feeds)
             o[k - 1].ptr = chain;
@@ -1958,8 +2014,9 @@ run_tiled(aqz_ds* ds,
             return ds->fail_arg(w + ": level " + std::to_string(L - 1) +
                                 " is narrower than one vector load (" + std::to_string(a.width) +
                                 " px)");
-        const hipError_t e = aqz::launch_cascade_tiled(ds->dtype, ds->method, src, a_elems, a.width,
-                                                       a.height, o, t, int(k), n_frames, stream);
+        const hipError_t e =
+          aqz::launch_cascade_tiled(ds->dtype, ds->method, src, a_elems, a.width, a.height, o, t,
+                                    int(k), n_frames, stream, with_base ? &t0 : nullptr);
         if (e != hipSuccess)
             return e == hipErrorInvalidValue ? ds->fail_arg(w + ": unsupported geometry")
                                              : ds->fail(e, "batch tiled cascade");
@@ -1971,7 +2028,7 @@ run_tiled(aqz_ds* ds,
         if (out_counts)
             out_counts[l] = n_frames;
     }
-    ds->last_batch_kind = 4;
+    ds->last_batch_kind = base ? 6 : 4;
     return AQZ_OK;
 }
 
@@ -2223,6 +2280,62 @@ aqz_ds_run_device_batch_chunked(aqz_ds* ds,
     } catch (...) {
         return ABI_GUARD_FAIL(ds);
     }
+}
+
+int
+aqz_ds_run_device_batch_tiled_base(aqz_ds* ds,
+                                   const void* device_frames,
+                                   uint32_t n_frames,
+                                   const uint32_t* tile_rows,
+                                   const uint32_t* tile_cols,
+                                   void* const* device_out_levels,
+                                   uint8_t* const* device_tile_nonzero,
+                                   uint32_t* out_counts,
+                                   void* hip_stream)
+{
+    try {
+        if (!ds)
+            return AQZ_INVALID_ARGUMENT;
+        return run_tiled(ds, "run_device_batch_tiled_base", device_frames, n_frames, tile_rows,
+                         tile_cols, device_out_levels, nullptr, device_tile_nonzero, out_counts,
+                         hip_stream, true);
+    } catch (...) {
+        return ABI_GUARD_FAIL(ds);
+    }
+}
+
+int
+aqz_ds_run_device_batch_chunked_base(aqz_ds* ds,
+                                     const void* device_frames,
+                                     uint32_t n_frames,
+                                     const aqz_chunk_lattice* lattices,
+                                     uint8_t* const* device_tile_nonzero,
+                                     uint32_t* out_counts,
+                                     void* hip_stream)
+{
+    try {
+        if (!ds)
+            return AQZ_INVALID_ARGUMENT;
+        if (!lattices)
+            return ds->fail_arg("run_device_batch_chunked_base: null lattices");
+        return run_tiled(ds, "run_device_batch_chunked_base", device_frames, n_frames, nullptr,
+                         nullptr, nullptr, lattices, device_tile_nonzero, out_counts, hip_stream,
+                         true);
+    } catch (...) {
+        return ABI_GUARD_FAIL(ds);
+    }
+}
+
+uint32_t
+aqz_ds_tiled_base_flag_slots(const aqz_ds* ds, uint32_t tile_rows, uint32_t tile_cols)
+{
+    if (!ds || ds->n < 2 || tile_rows == 0 || tile_cols == 0)
+        return 0;
+    // level 0 leaves with the first fused run: levels 1 .. min(n - 1, 4)
+    const uint32_t k = std::min<uint32_t>(ds->n - 1, aqz::kMaxFusedLevels);
+    const uint32_t s = aqz::cascade_tiled_base_slots(ds->dtype, ds->lv[0].desc.width, int(k),
+                                                     tile_rows, tile_cols, nullptr);
+    return s ? s : 1;
 }
 
 int

@@ -426,7 +426,8 @@ int aqz_ds_run_device_batch(aqz_ds* ds,
  * S = aqz_ds_tiled_flag_slots(ds, L, tile_rows[L], tile_cols[L]) flag bytes
  * per tile (tile-major, n_tiles(L) * S bytes per frame): a tile holds a
  * nonzero byte iff any of its S bytes is nonzero.  Index 0 of every array is
- * ignored.  One kernel per 4 levels writes the levels from registers — no
+ * ignored (aqz_ds_run_device_batch_tiled_base writes level 0 as well).  One
+ * kernel per 4 levels writes the levels from registers — no
  * row-major pass, no tiling pass — and its trailing waves zero the tile
  * overhang; when S > 1 every flag byte is written once by the wave that owns
  * it, so nothing is cleared first (S == 1: one byte per tile, cleared by a
@@ -507,6 +508,69 @@ int aqz_ds_run_device_batch_chunked(aqz_ds* ds,
                                     uint8_t* const* device_tile_nonzero,
                                     uint32_t* out_counts,
                                     void* hip_stream);
+
+/*
+ * aqz_ds_run_device_batch_tiled / _chunked with the full-resolution level
+ * written as chunk tiles by the same kernel: index 0 of tile_rows, tile_cols,
+ * device_out_levels and device_tile_nonzero (of `lattices` in the chunked
+ * form) is honoured.  Frame k of level 0 goes to device_out_levels[0] +
+ * k * n_tiles(0) * tile_rows[0] * tile_cols[0] * bytes_of_type — or tile t at
+ * lattices[0].frame_offset_bytes[k] + t * chunk_stride_bytes, with n_frames
+ * offsets from aqz_chunk_frame_offsets on level 0's own dimensions — in the
+ * layout, with the zero overhang and flag semantics, documented above for the
+ * other levels; device_tile_nonzero[0] (optional like the others) holds
+ * aqz_ds_tiled_base_flag_slots(ds, tile_rows[0], tile_cols[0]) bytes per
+ * tile.  Every wave of the first fused run stores the block it has loaded
+ * (2^n rows x 64 lanes, n = levels of that run) as tiles before it reduces
+ * it, so the batch is read once: no aqz_tile_frame_device pass per frame.
+ * Levels >= 1, `out_counts` and the handle's per-level counts are byte for
+ * byte those of aqz_ds_run_device_batch_tiled / _chunked on the same input;
+ * later runs of a deeper pyramid do not touch level 0's output.
+ * Accepted: what those calls accept, plus a non-null base output and a
+ * nonzero base tile shape; the chunked form checks lattices[0] like the
+ * other levels.  Anything else is AQZ_INVALID_ARGUMENT with a message naming
+ * level 0, before anything is queued (every fused run of a deeper pyramid is
+ * checked first, so a level 4 narrower than one load refuses the whole call
+ * with nothing written); there is no fallback.  Volume pyramids
+ * are refused (aqz_ds_run_device_volume_tiled keeps ignoring index 0).
+ * Stream rules as for the calls without the base.  aqz_ds_last_batch_kind
+ * reports 6.
+ * Measured on one MI355X (64 frames, 256 x 256 tiles, against
+ * the call without the base plus one aqz_tile_frame_device_sliced per frame):
+ * 4096^2 u16 Mean 0.862 against 1.312 ms, Decimate 0.845 against 1.130,
+ * 3000^2 u16 Mean 0.500 against 0.840, 4096^2 f32 Mean 1.656 against 2.524,
+ * 3000^2 f32 Mean 1.032 against 1.483: on every workload below by far more
+ * than the spread.
+ */
+int aqz_ds_run_device_batch_tiled_base(aqz_ds* ds,
+                                       const void* device_frames,
+                                       uint32_t n_frames,
+                                       const uint32_t* tile_rows,
+                                       const uint32_t* tile_cols,
+                                       void* const* device_out_levels,
+                                       uint8_t* const* device_tile_nonzero,
+                                       uint32_t* out_counts,
+                                       void* hip_stream);
+
+int aqz_ds_run_device_batch_chunked_base(aqz_ds* ds,
+                                         const void* device_frames,
+                                         uint32_t n_frames,
+                                         const aqz_chunk_lattice* lattices,
+                                         uint8_t* const* device_tile_nonzero,
+                                         uint32_t* out_counts,
+                                         void* hip_stream);
+
+/*
+ * Flag bytes per tile that aqz_ds_run_device_batch_tiled_base writes for
+ * level 0 with tile_rows x tile_cols tiles: aqz_ds_tiled_flag_slots' rule
+ * for the first fused run's own input — wave blocks of 2^n rows (n = levels
+ * of that run, at most 4) by 64 lanes' columns, one lane store being the
+ * lane's whole load.  S > 1 (or 1 with nothing cleared) where blocks and
+ * tiles nest, else one byte per tile cleared by a fill queued ahead of the
+ * kernel.  0 for a bad shape, a null handle or a one-level handle.
+ * (aqz_ds_tiled_flag_slots(ds, 0, ...) keeps returning 0.)
+ */
+uint32_t aqz_ds_tiled_base_flag_slots(const aqz_ds* ds, uint32_t tile_rows, uint32_t tile_cols);
 
 /*
  * aqz_ds_run_device_batch_tiled / _chunked for volume pyramids: every level
@@ -608,6 +672,8 @@ int aqz_ds_run_host_batch(aqz_ds* ds,
  * element-aligned; the fused kernels take any other width and offset),
  * 4 = fused 2-D cascade writing chunk tiles (aqz_ds_run_device_batch_tiled),
  * 5 = fused volume writing chunk tiles (aqz_ds_run_device_volume_tiled),
+ * 6 = fused 2-D cascade writing chunk tiles, base included
+ * (aqz_ds_run_device_batch_tiled_base / _chunked_base),
  * -1 = none.
  */
 int aqz_ds_last_batch_kind(const aqz_ds* ds);
