@@ -66,6 +66,9 @@ EXPORTS = (
     "aqz_zarr_shard_set_append_layer", "aqz_zarr_shard_set_tables",
     "aqz_zarr_shard_chunk_has_data_device", "aqz_debug_zarr_shard_d2h_bytes",
     "aqz_debug_zarr_shard_set_file_offsets", "aqz_debug_zarr_shard_pack_device",
+    "aqz_blosc_frame_info", "aqz_blosc_unfilter_device", "aqz_blosc_lz4_decompress_device",
+    "aqz_zarr_shard_decompress_device", "aqz_debug_lz4_decode_host",
+    "aqz_debug_blosc_decode_host", "aqz_debug_lz4_decode_blocks_device",
 )
 
 
@@ -126,6 +129,17 @@ class ZarrShardGeometry(ctypes.Structure):
     """aqz_zarr_shard_geometry (include/aqz_shard.h)."""
     _fields_ = [("n_shards", ctypes.c_uint32), ("chunks_per_shard", ctypes.c_uint32),
                 ("chunks_per_layer", ctypes.c_uint32), ("layers_per_shard", ctypes.c_uint32)]
+
+
+class BloscFrameHeader(ctypes.Structure):
+    """aqz_blosc_frame_header (include/aqz_blosc.h)."""
+    _fields_ = [("status", ctypes.c_uint32),
+                ("version", ctypes.c_uint8), ("versionlz", ctypes.c_uint8),
+                ("flags", ctypes.c_uint8), ("typesize", ctypes.c_uint8),
+                ("nbytes", ctypes.c_uint32), ("blocksize", ctypes.c_uint32),
+                ("cbytes", ctypes.c_uint32), ("memcpyed", ctypes.c_uint32),
+                ("shuffle", ctypes.c_uint32), ("nsplits", ctypes.c_uint32),
+                ("nblocks", ctypes.c_uint32)]
 
 
 _lib = None
@@ -277,6 +291,14 @@ def lib() -> ctypes.CDLL:
     L.aqz_debug_zarr_shard_d2h_bytes.restype = ctypes.c_uint64
     L.aqz_debug_zarr_shard_set_file_offsets.argtypes = [vp, u64p, vp]
     L.aqz_debug_zarr_shard_pack_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, u32, i32, vp, vp]
+    L.aqz_blosc_frame_info.argtypes = [vp, sz, u32, sz, ctypes.POINTER(BloscFrameHeader)]
+    L.aqz_blosc_unfilter_device.argtypes = [ctypes.c_int, u32, u32, vp, sz, u32, vp, vp]
+    L.aqz_blosc_lz4_decompress_device.argtypes = [vp, u32, sz, vp, sz, vp, u32, vp, sz, vp, vp]
+    L.aqz_zarr_shard_decompress_device.argtypes = [vp, u32, sz, vp, sz, ctypes.c_uint64, vp, u32,
+                                                   vp, sz, vp, vp]
+    L.aqz_debug_lz4_decode_host.argtypes = [vp, sz, vp, sz]
+    L.aqz_debug_blosc_decode_host.argtypes = [vp, sz, u32, sz, vp, ctypes.POINTER(u32)]
+    L.aqz_debug_lz4_decode_blocks_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]
     _lib = L
     return L
 
@@ -910,7 +932,85 @@ class BloscContext:
             ctypes.c_void_p(stream) if stream else None, flags))
 
 
+    def lz4_decompress_device(self, typesize: int, nbytes: int, device_frames: int,
+                              frame_stride: int, device_frame_bytes: int, n_frames: int,
+                              device_dst: int, dst_stride: int, device_status: int,
+                              stream: int = 0):
+        """aqz_blosc_lz4_decompress_device: frame k at device_frames + k *
+        frame_stride (size from the device uint32 array, 0 for the header's)
+        into chunk k at device_dst + k * dst_stride, status in the device
+        uint32 array `device_status`; asynchronous on `stream`."""
+        _raise_if(lib().aqz_blosc_lz4_decompress_device(
+            self._h, typesize, nbytes, device_frames, frame_stride, device_frame_bytes or None,
+            n_frames, device_dst, dst_stride, device_status,
+            ctypes.c_void_p(stream) if stream else None))
+
+    def zarr_shard_decompress_device(self, typesize: int, nbytes: int, device_shard_bytes: int,
+                                     shard_bytes: int, base_file_offset: int, device_table: int,
+                                     n_chunks: int, device_dst: int, dst_stride: int,
+                                     device_status: int, stream: int = 0):
+        """aqz_zarr_shard_decompress_device (asynchronous on `stream`)."""
+        _raise_if(lib().aqz_zarr_shard_decompress_device(
+            self._h, typesize, nbytes, device_shard_bytes, shard_bytes, base_file_offset,
+            device_table, n_chunks, device_dst, dst_stride, device_status,
+            ctypes.c_void_p(stream) if stream else None))
+
+    def debug_lz4_decode_blocks_device(self, device_comp: int, device_comp_offsets: int,
+                                       device_csize: int, device_out: int,
+                                       device_out_offsets: int, device_cap: int, device_results: int,
+                                       n_blocks: int, stream: int = 0):
+        """aqz_debug_lz4_decode_blocks_device: one wave per bare LZ4 block,
+        asynchronous on `stream`."""
+        _raise_if(lib().aqz_debug_lz4_decode_blocks_device(
+            self._h, device_comp, device_comp_offsets, device_csize, device_out,
+            device_out_offsets, device_cap, device_results, n_blocks,
+            ctypes.c_void_p(stream) if stream else None))
+
+
 LZ4_PROBE_SERIAL = 1  # aqz_blosc.h
+
+# per-frame status of the decompress calls (AQZ_BLOSC_FRAME_*, aqz_blosc.h)
+FRAME_OK, FRAME_ABSENT, FRAME_BAD_HEADER, FRAME_UNSUPPORTED, FRAME_CORRUPT = range(5)
+
+
+def blosc_unfilter_device(shuffle: int, typesize: int, blocksize: int, device_src: int,
+                          nbytes: int, n_buffers: int, device_dst: int, stream: int = 0):
+    """aqz_blosc_unfilter_device (asynchronous on `stream`)."""
+    _raise_if(lib().aqz_blosc_unfilter_device(shuffle, typesize, blocksize, device_src, nbytes,
+                                              n_buffers, device_dst,
+                                              ctypes.c_void_p(stream) if stream else None))
+
+
+def debug_lz4_decode_host(block, cap: int):
+    """aqz_debug_lz4_decode_host: (return value, the `cap` output bytes) of
+    the serial LZ4 block decoder; the output array is exactly `cap` long and
+    starts out as 0xA5."""
+    s = np.frombuffer(bytes(block), np.uint8)
+    dst = np.full(cap, 0xA5, np.uint8)
+    n = lib().aqz_debug_lz4_decode_host(s.ctypes.data if s.size else None, s.size,
+                                        dst.ctypes.data if cap else None, cap)
+    return n, dst
+
+
+def blosc_frame_info(frame, typesize: int = 0, nbytes: int = 0) -> dict:
+    """aqz_blosc_frame_info on host bytes: the header fields and status."""
+    s = np.frombuffer(bytes(frame), np.uint8)
+    h = BloscFrameHeader()
+    _raise_if(lib().aqz_blosc_frame_info(s.ctypes.data if s.size else None, s.size, typesize,
+                                         nbytes, ctypes.byref(h)))
+    return {k: getattr(h, k) for k, _ in BloscFrameHeader._fields_}
+
+
+def debug_blosc_decode_host(frame, typesize: int, nbytes: int):
+    """aqz_debug_blosc_decode_host: (status, the nbytes output bytes, 0xA5
+    where nothing was written)."""
+    s = np.frombuffer(bytes(frame), np.uint8)
+    dst = np.full(nbytes, 0xA5, np.uint8)
+    st = ctypes.c_uint32()
+    _raise_if(lib().aqz_debug_blosc_decode_host(s.ctypes.data if s.size else None, s.size,
+                                                typesize, nbytes, dst.ctypes.data,
+                                                ctypes.byref(st)))
+    return st.value, dst
 
 
 def debug_lz4_block_host(src, cap: int, accel: int):

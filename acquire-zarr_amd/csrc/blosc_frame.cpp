@@ -26,8 +26,11 @@
 // the same liblz4 / libzstd this file loads) byte for byte:
 // tests/test_blosc_frames.py.
 #include "aqz_blosc.h"
+#include "aqz_shard.h"
 #include "abi_guard.hh"
+#include "blosc_decode.hh"
 #include "codec_kernels.hh"
+#include "hip_raii.hh"
 #include "lz4_block.hh"
 
 #include <hip/hip_runtime.h>
@@ -350,6 +353,9 @@ struct aqz_blosc_ctx
     uint8_t* h_table = nullptr; // pinned: sizes, then offsets
     size_t h_table_cap = 0;
     uint64_t d2h_bytes = 0; // of the last aqz_blosc_lz4_compress_device
+    // aqz_blosc_lz4_decompress_device / aqz_zarr_shard_decompress_device
+    aqz::DeviceBuf d_decoded; // the filtered chunks, ahead of the unfilter
+    aqz::DeviceBuf d_meta;    // (filter, blocksize) per frame
 };
 
 namespace {
@@ -379,6 +385,8 @@ release(aqz_blosc_ctx* c)
     }
     c->comp_cap = c->rows_cap = c->frames_cap = c->table_cap = 0;
     c->h_packed_cap = c->h_table_cap = 0;
+    c->d_decoded.reset();
+    c->d_meta.reset();
 }
 
 int
@@ -884,6 +892,205 @@ aqz_blosc_compress_device(aqz_blosc_ctx* ctx, int clevel, int shuffle, uint32_t 
         }
         // chunks c-blosc would store unfiltered (incompressible ones)
         return copy_raw(src, nbytes, dst, dst_stride, raw_ids);
+    } catch (...) {
+        return ABI_GUARD_FAIL(nullptr);
+    }
+}
+
+// ---- reading the frames back -------------------------------------------------
+
+int
+aqz_debug_lz4_decode_host(const void* src, size_t n, void* dst, size_t cap)
+{
+    try {
+        if ((!src && n) || (!dst && cap) || n > 0x7FFFFFFFu) {
+            aqz::set_last_error("debug_lz4_decode_host: invalid argument");
+            return -100;
+        }
+        return aqz::lz4::decode_block(static_cast<const uint8_t*>(src), static_cast<uint32_t>(n),
+                                      static_cast<uint8_t*>(dst),
+                                      static_cast<uint32_t>(std::min<size_t>(cap, 0x7FFFFFFFu)));
+    } catch (...) {
+        (void)ABI_GUARD_FAIL(nullptr);
+        return -100;
+    }
+}
+
+int
+aqz_blosc_frame_info(const void* frame, size_t extent, uint32_t typesize, size_t nbytes,
+                     aqz_blosc_frame_header* out)
+{
+    try {
+        if (!out || (!frame && extent) || nbytes > kMaxBuffer) {
+            aqz::set_last_error("blosc_frame_info: invalid argument");
+            return AQZ_INVALID_ARGUMENT;
+        }
+        aqz::blosc::FrameInfo fi{};
+        const auto st = aqz::blosc::parse_header(static_cast<const uint8_t*>(frame), extent,
+                                                 typesize, static_cast<uint32_t>(nbytes), &fi);
+        *out = aqz_blosc_frame_header{ st,           fi.version,   fi.versionlz, fi.flags,
+                                       fi.typesize,  fi.nbytes,    fi.blocksize, fi.cbytes,
+                                       fi.memcpyed,  fi.filter,    fi.nsplits,   fi.nblocks };
+        return AQZ_OK;
+    } catch (...) {
+        return ABI_GUARD_FAIL(nullptr);
+    }
+}
+
+int
+aqz_debug_blosc_decode_host(const void* frame, size_t extent, uint32_t typesize, size_t nbytes,
+                            void* dst, uint32_t* status)
+{
+    try {
+        if (!status || !dst || (!frame && extent) || typesize == 0 || nbytes == 0 ||
+            nbytes > kMaxBuffer) {
+            aqz::set_last_error("debug_blosc_decode_host: invalid argument");
+            return AQZ_INVALID_ARGUMENT;
+        }
+        std::vector<uint8_t> scratch(nbytes);
+        aqz::blosc::FrameInfo fi{};
+        *status = aqz::blosc::decode_frame_serial(static_cast<const uint8_t*>(frame), extent,
+                                                  typesize, static_cast<uint32_t>(nbytes),
+                                                  static_cast<uint8_t*>(dst), scratch.data(), &fi);
+        return AQZ_OK;
+    } catch (...) {
+        return ABI_GUARD_FAIL(nullptr);
+    }
+}
+
+int
+aqz_blosc_unfilter_device(int shuffle, uint32_t typesize, uint32_t blocksize,
+                          const void* device_src, size_t nbytes, uint32_t n_buffers,
+                          void* device_dst, void* hip_stream)
+{
+    try {
+        if (!device_src || !device_dst || typesize == 0 || blocksize == 0 || n_buffers == 0 ||
+            shuffle < AQZ_BLOSC_NOSHUFFLE || shuffle > AQZ_BLOSC_BITSHUFFLE ||
+            nbytes > 0x7FFFFFFFu) {
+            aqz::set_last_error("blosc_unfilter_device: invalid argument");
+            return AQZ_INVALID_ARGUMENT;
+        }
+        BLOSC_HIP(aqz::launch_blosc_unfilter(shuffle, typesize, blocksize, device_src, nbytes,
+                                             static_cast<uint32_t>(nbytes), n_buffers, device_dst,
+                                             nbytes, nullptr,
+                                             static_cast<hipStream_t>(hip_stream)),
+                  "unfilter");
+        return AQZ_OK;
+    } catch (...) {
+        return ABI_GUARD_FAIL(nullptr);
+    }
+}
+
+int
+aqz_debug_lz4_decode_blocks_device(aqz_blosc_ctx* ctx, const void* device_comp,
+                                   const uint64_t* device_comp_offsets,
+                                   const uint32_t* device_csize, void* device_out,
+                                   const uint64_t* device_out_offsets, const uint32_t* device_cap,
+                                   int32_t* device_results, uint32_t n_blocks, void* hip_stream)
+{
+    try {
+        if (!ctx || !device_comp || !device_comp_offsets || !device_csize || !device_out ||
+            !device_out_offsets || !device_cap || !device_results || n_blocks == 0) {
+            aqz::set_last_error("debug_lz4_decode_blocks_device: invalid argument");
+            return AQZ_INVALID_ARGUMENT;
+        }
+        int prev = 0;
+        (void)hipGetDevice(&prev);
+        struct Restore
+        {
+            int d;
+            ~Restore() { (void)hipSetDevice(d); }
+        } restore{ prev };
+        BLOSC_HIP(hipSetDevice(ctx->device), "set device");
+        BLOSC_HIP(aqz::launch_lz4_decode_blocks(device_comp, device_comp_offsets, device_csize,
+                                                device_out, device_out_offsets, device_cap,
+                                                device_results, n_blocks,
+                                                static_cast<hipStream_t>(hip_stream)),
+                  "lz4 decode");
+        return AQZ_OK;
+    } catch (...) {
+        return ABI_GUARD_FAIL(nullptr);
+    }
+}
+
+namespace {
+
+// The shared tail of the two decompress calls: scratch, then the queue.
+int
+queue_decode(aqz_blosc_ctx* ctx, aqz::BloscDecodeCall call, uint32_t n_frames, void* hip_stream)
+{
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    struct Restore
+    {
+        int d;
+        ~Restore() { (void)hipSetDevice(d); }
+    } restore{ prev };
+    BLOSC_HIP(hipSetDevice(ctx->device), "set device");
+    BLOSC_HIP(ctx->d_decoded.reserve(size_t(call.nbytes) * n_frames), "device scratch");
+    BLOSC_HIP(ctx->d_meta.reserve(2 * sizeof(uint32_t) * size_t(n_frames)), "device scratch");
+    call.scratch = ctx->d_decoded.bytes();
+    call.meta = static_cast<uint32_t*>(ctx->d_meta.get());
+    BLOSC_HIP(aqz::launch_blosc_decode(call, n_frames, static_cast<hipStream_t>(hip_stream)),
+              "decode");
+    return AQZ_OK;
+}
+
+} // namespace
+
+int
+aqz_blosc_lz4_decompress_device(aqz_blosc_ctx* ctx, uint32_t typesize, size_t nbytes,
+                                const void* device_frames, size_t frame_stride,
+                                const uint32_t* device_frame_bytes, uint32_t n_frames,
+                                void* device_dst, size_t dst_stride, uint32_t* device_status,
+                                void* hip_stream)
+{
+    try {
+        if (!ctx || !device_frames || !device_dst || !device_status || typesize == 0 ||
+            nbytes == 0 || n_frames == 0 || dst_stride < nbytes || nbytes > kMaxBuffer) {
+            aqz::set_last_error("blosc_lz4_decompress_device: invalid argument");
+            return AQZ_INVALID_ARGUMENT;
+        }
+        aqz::BloscDecodeCall call{};
+        call.frames = static_cast<const uint8_t*>(device_frames);
+        call.frame_stride = frame_stride;
+        call.frame_bytes = device_frame_bytes;
+        call.dst = static_cast<uint8_t*>(device_dst);
+        call.dst_stride = dst_stride;
+        call.status = device_status;
+        call.typesize = typesize > 255 ? 1u : typesize;
+        call.nbytes = static_cast<uint32_t>(nbytes);
+        return queue_decode(ctx, call, n_frames, hip_stream);
+    } catch (...) {
+        return ABI_GUARD_FAIL(nullptr);
+    }
+}
+
+int
+aqz_zarr_shard_decompress_device(aqz_blosc_ctx* ctx, uint32_t typesize, size_t nbytes,
+                                 const void* device_shard_bytes, size_t shard_bytes,
+                                 uint64_t base_file_offset, const uint64_t* device_table,
+                                 uint32_t n_chunks, void* device_dst, size_t dst_stride,
+                                 uint32_t* device_status, void* hip_stream)
+{
+    try {
+        if (!ctx || !device_shard_bytes || !device_table || !device_dst || !device_status ||
+            typesize == 0 || nbytes == 0 || n_chunks == 0 || dst_stride < nbytes ||
+            nbytes > kMaxBuffer) {
+            aqz::set_last_error("zarr_shard_decompress_device: invalid argument");
+            return AQZ_INVALID_ARGUMENT;
+        }
+        aqz::BloscDecodeCall call{};
+        call.frames = static_cast<const uint8_t*>(device_shard_bytes);
+        call.frame_stride = shard_bytes;
+        call.table = reinterpret_cast<const uint8_t*>(device_table);
+        call.base = base_file_offset;
+        call.dst = static_cast<uint8_t*>(device_dst);
+        call.dst_stride = dst_stride;
+        call.status = device_status;
+        call.typesize = typesize > 255 ? 1u : typesize;
+        call.nbytes = static_cast<uint32_t>(nbytes);
+        return queue_decode(ctx, call, n_chunks, hip_stream);
     } catch (...) {
         return ABI_GUARD_FAIL(nullptr);
     }

@@ -84,4 +84,64 @@ hipError_t launch_pack_frames(const void* frames,
                               uint32_t n_buffers,
                               hipStream_t stream);
 
+// ---- reading the frames back (aqz_blosc_lz4_decompress_device) --------------
+
+// blosc_d's unfilter step, the inverse of launch_blosc_filter with the same
+// block rules: buffer k from src + k * src_stride to dst + k * dst_stride.
+// `meta` null: every buffer has `shuffle` and `blocksize`.  Else buffer k
+// takes them from the pair meta[2k] (1 byte shuffle, 2 bit shuffle, 0: the
+// buffer is left alone) and meta[2k + 1], as launch_blosc_decode writes them.
+hipError_t launch_blosc_unfilter(int shuffle,
+                                 uint32_t typesize,
+                                 uint32_t blocksize,
+                                 const void* src,
+                                 uint64_t src_stride,
+                                 uint32_t nbytes,
+                                 uint32_t n_buffers,
+                                 void* dst,
+                                 uint64_t dst_stride,
+                                 const uint32_t* meta,
+                                 hipStream_t stream);
+
+// LZ4_decompress_safe(split k, out k, csize[k], cap[k]) for `n_splits` blocks,
+// one wave each (blosc_decode.hh states the decoder): block k is
+// comp[comp_offsets[k], + csize[k]), its output goes to out + out_offsets[k],
+// results[k] is the decoded size or the lz4::DecodeError.
+hipError_t launch_lz4_decode_blocks(const void* comp,
+                                    const uint64_t* comp_offsets,
+                                    const uint32_t* csize,
+                                    void* out,
+                                    const uint64_t* out_offsets,
+                                    const uint32_t* cap,
+                                    int32_t* results,
+                                    uint32_t n_splits,
+                                    hipStream_t stream);
+
+struct BloscDecodeCall
+{
+    // strided form: frame k at frames + k * frame_stride, its size in
+    // frame_bytes[k] (null: from the header)
+    const uint8_t* frames;
+    uint64_t frame_stride;
+    const uint32_t* frame_bytes;
+    // shard form (table non-null): (offset, extent) pair k; frames = the
+    // shard's bytes, frame_stride = their count, base = their file offset
+    const uint8_t* table;
+    uint64_t base;
+    uint8_t* dst; // chunk k at dst + k * dst_stride
+    uint64_t dst_stride;
+    uint8_t* scratch; // n_frames * nbytes: the filtered chunks
+    uint32_t* meta;   // n_frames pairs for launch_blosc_unfilter
+    uint32_t* status; // blosc::Status per frame
+    uint32_t typesize;
+    uint32_t nbytes;
+};
+
+// Header parse, split decode, raw-split and memcpy copies (one kernel, a
+// fixed number of waves per frame walking its splits), then the per-frame
+// unfilter.  Nothing is read back: the geometry follows from typesize, nbytes
+// and n_frames.
+hipError_t launch_blosc_decode(const BloscDecodeCall& call, uint32_t n_frames,
+                               hipStream_t stream);
+
 } // namespace aqz

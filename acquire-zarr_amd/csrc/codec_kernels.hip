@@ -16,6 +16,7 @@
 // bitshuffle-generic.c; RFC 3720 CRC-32C); the CPU restatement the tests
 // compare against is oracle/codec_oracle.c.
 #include "codec_kernels.hh"
+#include "blosc_decode.hh"
 #include "launch_log.hh"
 #include "lz4_block.hh"
 
@@ -1272,6 +1273,525 @@ launch_pack_frames(const void* frames, uint64_t stride, const uint32_t* sizes,
                        static_cast<const uint8_t*>(frames), stride, sizes, offsets,
                        static_cast<uint8_t*>(packed));
     return hipGetLastError();
+}
+
+// ---- reading blosc+LZ4 frames back -------------------------------------------
+//
+// blosc_decode.hh states the frame walk, the LZ4 block decoder and the
+// unfilter serially.  Here one wave decodes one split: the token walk is
+// wave-uniform (every value that steers it comes out of a lane read), and the
+// 64 lanes share the literal and match copies.  Every bound is checked before
+// the copy it guards, as in the serial decoder, so a malformed stream ends in
+// a status.
+//
+// A match reads bytes this wave may just have stored, through other lanes.
+// The output lives in global memory; a workgroup-scope fence (one wave sits on
+// one CU) orders those stores before the loads, and is paid only when the
+// match's source reaches past `visible`, the position up to which an earlier
+// fence already covers.  No non-temporal stores: the region is read again.
+// DESIGN.md §12.13 has the reasons against an LDS window.
+
+namespace {
+
+typedef unsigned long long u64_u __attribute__((aligned(1)));
+typedef unsigned int u32_u __attribute__((aligned(1)));
+
+// 256 bytes of a split's input held by the wave, four per lane; a byte is a
+// lane read away.  `i` is wave-uniform.
+struct InWindow
+{
+    const uint8_t* src;
+    uint32_t n, lane, base, word;
+
+    __device__ __forceinline__ void fill(uint32_t at)
+    {
+        base = at;
+        const uint32_t p = at + 4 * lane; // at < n <= 2^31
+        uint32_t w = 0;
+        if (p + 4 <= n) {
+            w = lz4::read32(src + p);
+        } else {
+            for (uint32_t k = 0; k < 4 && p + k < n; ++k)
+                w |= uint32_t(src[p + k]) << (8 * k);
+        }
+        word = w;
+    }
+    __device__ __forceinline__ uint32_t operator()(uint32_t i)
+    {
+        i = uni(i);
+        if (i - base >= 256u)
+            fill(i);
+        const uint32_t d = i - base;
+        return (lane_read(word, d >> 2) >> (8 * (d & 3))) & 0xFFu;
+    }
+};
+
+// dst[0, len) = src[0, len), ranges apart, any alignment: 16 bytes a lane,
+// the last 15 or fewer one byte a lane
+__device__ __forceinline__ void
+wave_copy16(uint8_t* dst, const uint8_t* src, uint32_t len, uint32_t lane)
+{
+    const uint32_t vecs = len >> 4;
+    for (uint32_t i = lane; i < vecs; i += 64)
+        *reinterpret_cast<u32x4_u*>(dst + 16 * uint64_t(i)) =
+          *reinterpret_cast<const u32x4_u*>(src + 16 * uint64_t(i));
+    const uint32_t t = (vecs << 4) + lane;
+    if (t < len)
+        dst[t] = src[t];
+}
+
+// out[pos + i] = out[pos - off + i % off], i < len, for a match that overlaps
+// itself (off < len): every source lies before pos, so one pass suffices.
+// Four bytes a lane; i % off is divided once and stepped from there.
+__device__ __forceinline__ void
+wave_copy_periodic(uint8_t* out, uint32_t pos, uint32_t off, uint32_t len, uint32_t lane)
+{
+    const uint8_t* pat = out + (pos - off);
+    uint8_t* to = out + pos;
+    uint32_t r = (4 * lane) % off;
+    const uint32_t step = 256 % off;
+    for (uint32_t i0 = 4 * lane; i0 < len; i0 += 256) {
+        uint32_t q = r, w = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            w |= uint32_t(pat[q]) << (8 * k);
+            q = q + 1 == off ? 0 : q + 1;
+        }
+        if (i0 + 4 <= len) {
+            store32(to + i0, w);
+        } else {
+            for (uint32_t k = 0; i0 + k < len; ++k)
+                to[i0 + k] = uint8_t(w >> (8 * k));
+        }
+        r += step;
+        if (r >= off)
+            r -= off;
+    }
+}
+
+// lz4::decode_block by one wave; the result is wave-uniform.
+__device__ __forceinline__ int32_t
+wave_decode_block(const uint8_t* src, uint32_t n, uint8_t* out, uint32_t cap, uint32_t lane)
+{
+    if (n == 0)
+        return lz4::kDecEmpty;
+    if (cap > 0x7FFFFFFFu)
+        cap = 0x7FFFFFFFu;
+    InWindow rd{ src, n, lane, 0, 0 };
+    rd.fill(0);
+    uint32_t ip = 0, op = 0, visible = 0;
+    for (;;) {
+        const uint32_t token = rd(ip++);
+        uint64_t lit;
+        if (const int32_t e = lz4::read_run(rd, ip, n, token >> 4, lit))
+            return e;
+        if (lit > n - ip)
+            return lz4::kDecLiteralsInput;
+        if (lit > cap - op)
+            return lz4::kDecLiteralsOutput;
+        wave_copy16(out + op, src + ip, uint32_t(lit), lane);
+        ip += uint32_t(lit);
+        op += uint32_t(lit);
+        if (ip == n)
+            return int32_t(op);
+        if (n - ip < 2)
+            return lz4::kDecTruncated;
+        const uint32_t off = rd(ip) | (rd(ip + 1) << 8);
+        ip += 2;
+        uint64_t ml64;
+        if (const int32_t e = lz4::read_run(rd, ip, n, token & 15, ml64))
+            return e;
+        ml64 += 4;
+        if (off == 0)
+            return lz4::kDecOffsetZero;
+        if (off > op)
+            return lz4::kDecOffsetBefore;
+        if (ml64 > cap - op)
+            return lz4::kDecMatchOutput;
+        const uint32_t ml = uint32_t(ml64);
+        // the source is out[op - off, op - off + min(off, ml)): fence when it
+        // holds bytes stored since the last fence
+        if (op - off + (off < ml ? off : ml) > visible) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            visible = op;
+        }
+        if (off >= ml)
+            wave_copy16(out + op, out + (op - off), ml, lane);
+        else
+            wave_copy_periodic(out, op, off, ml, lane);
+        op += ml;
+        if (ip >= n)
+            return lz4::kDecEndsInMatch;
+    }
+}
+
+__global__ __launch_bounds__(64) void
+lz4_decode_blocks_kernel(const uint8_t* comp, const uint64_t* __restrict__ comp_offsets,
+                         const uint32_t* __restrict__ csize, uint8_t* out,
+                         const uint64_t* __restrict__ out_offsets,
+                         const uint32_t* __restrict__ cap, int32_t* __restrict__ results)
+{
+    const uint32_t k = blockIdx.x, lane = threadIdx.x;
+    const int32_t r =
+      wave_decode_block(comp + comp_offsets[k], csize[k], out + out_offsets[k], cap[k], lane);
+    if (lane == 0)
+        results[k] = r;
+}
+
+__device__ __forceinline__ void
+wave_zero(uint8_t* dst, uint32_t len, uint32_t lane)
+{
+    const uint32_t vecs = len >> 4;
+    const u32x4 z = { 0u, 0u, 0u, 0u };
+    for (uint32_t i = lane; i < vecs; i += 64)
+        *reinterpret_cast<u32x4_u*>(dst + 16 * uint64_t(i)) = z;
+    const uint32_t t = (vecs << 4) + lane;
+    if (t < len)
+        dst[t] = 0;
+}
+
+constexpr uint32_t kUnfilterSkip = 0; // meta pair: nothing to unfilter
+constexpr uint32_t kUnfilterCopy = 3; // uniform form, shuffle 0
+
+// Wave w of frame k: the header (every wave of a frame parses it and comes
+// to the same answer), then splits w, w + waves, ... of the frame.  Statuses
+// meet in status[k] by atomicMax on top of the 0 (kOk) queued before the
+// kernel: they are numbered in the order of detection, and whatever one wave
+// finds beyond kOk is the frame's.
+__global__ __launch_bounds__(64) void
+blosc_decode_kernel(BloscDecodeCall c, uint32_t k0, uint32_t waves)
+{
+    const uint32_t lane = threadIdx.x;
+    const uint32_t k = k0 + blockIdx.x / waves, w = blockIdx.x % waves;
+    uint8_t* dst = c.dst + uint64_t(k) * c.dst_stride;
+    // this wave's slice of a whole-chunk copy or fill
+    const uint32_t slice = ((c.nbytes + waves - 1) / waves + 15u) & ~15u;
+    const uint64_t s0 = uint64_t(w) * slice;
+    const uint32_t slen = s0 >= c.nbytes ? 0u : (c.nbytes - uint32_t(s0) < slice ? c.nbytes - uint32_t(s0) : slice);
+
+    blosc::FrameSpan span;
+    blosc::Status st = c.table ? blosc::span_shard(c.table, k, c.frame_stride, c.base, &span)
+                               : blosc::span_strided(c.frames, c.frame_stride, c.frame_bytes, k, &span);
+    blosc::FrameInfo fi{};
+    const uint8_t* f = c.frames + span.offset;
+    if (st == blosc::kAbsent)
+        wave_zero(dst + s0, slen, lane); // Zarr's fill value here
+    else if (st == blosc::kOk)
+        st = blosc::parse_header(f, span.extent, c.typesize, c.nbytes, &fi);
+    const bool filtered = st == blosc::kOk && !fi.memcpyed && fi.filter != blosc::kNoFilter;
+    if (w == 0 && lane == 0) {
+        c.meta[2 * uint64_t(k)] = filtered ? fi.filter : kUnfilterSkip;
+        c.meta[2 * uint64_t(k) + 1] = fi.blocksize;
+        if (st != blosc::kOk)
+            atomicMax(c.status + k, uint32_t(st));
+    }
+    if (st != blosc::kOk)
+        return;
+    if (fi.memcpyed) {
+        wave_copy16(dst + s0, f + blosc::kHeaderBytes + s0, slen, lane);
+        return;
+    }
+    uint8_t* out = filtered ? c.scratch + uint64_t(k) * c.nbytes : dst;
+    for (uint32_t s = w; s < fi.total_splits; s += waves) {
+        blosc::SplitRef r;
+        bool ok = blosc::locate_split(fi, f, span.extent, s, &r) == blosc::kOk;
+        if (ok) {
+            if (r.csize == r.neb)
+                wave_copy16(out + r.dst, f + r.src, r.neb, lane);
+            else
+                ok = wave_decode_block(f + r.src, r.csize, out + r.dst, r.neb, lane) ==
+                     int32_t(r.neb);
+        }
+        if (!ok) {
+            if (lane == 0)
+                atomicMax(c.status + k, uint32_t(blosc::kCorrupt));
+            return;
+        }
+    }
+}
+
+// ---- unfilter ----------------------------------------------------------------
+//
+// A buffer's blocks are cut into units of E elements: 8 for the byte
+// unshuffle (TS 8-byte plane loads in, 8 * TS contiguous bytes out), 64 or 32
+// for the bit unshuffle (8 * TS row loads of 8 or 4 bytes), 16 bytes for
+// copied blocks.  A block's last unit also copies its blocksize % typesize
+// tail.  Threads stride over a buffer's units, so any block size a header
+// names is covered by a grid sized from (typesize, nbytes) alone.  TS 0: any
+// typesize, byte by byte.
+
+template<int TS>
+constexpr uint32_t kBitUnitElems = (TS == 1 || TS == 2 || TS == 4) ? 64u : (TS == 8 ? 32u : 8u);
+
+struct UnfilterCall
+{
+    const uint8_t* src;
+    uint64_t src_stride;
+    uint8_t* dst;
+    uint64_t dst_stride;
+    const uint32_t* meta; // null: mode and bs below
+    uint32_t mode;        // 1 byte, 2 bit, kUnfilterCopy
+    uint32_t bs;
+    uint32_t ts;
+    uint32_t nbytes;
+    uint32_t blocks_per; // workgroups per buffer
+    uint32_t k0;
+};
+
+template<int TS>
+__device__ __forceinline__ void
+unshuffle_unit(const uint8_t* sb, uint8_t* db, uint32_t ts, uint32_t ne, uint32_t q)
+{
+    const uint32_t e0 = q * 8;
+    const uint32_t cnt = ne - e0 < 8 ? ne - e0 : 8;
+    if constexpr (TS >= 2) {
+        if (cnt == 8) {
+            uint64_t plane[TS];
+#pragma unroll
+            for (int j = 0; j < TS; ++j)
+                plane[j] = *reinterpret_cast<const u64_u*>(sb + uint64_t(j) * ne + e0);
+            uint8_t e[8 * TS];
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+#pragma unroll
+                for (int j = 0; j < TS; ++j)
+                    e[k * TS + j] = uint8_t(plane[j] >> (8 * k));
+            u32x4 v[TS / 2];
+            __builtin_memcpy(v, e, sizeof(e));
+            auto* d = reinterpret_cast<u32x4_u*>(db + uint64_t(e0) * TS);
+#pragma unroll
+            for (int i = 0; i < TS / 2; ++i)
+                d[i] = v[i];
+            return;
+        }
+    }
+    for (uint32_t k = 0; k < cnt; ++k)
+        for (uint32_t j = 0; j < ts; ++j)
+            db[uint64_t(e0 + k) * ts + j] = sb[uint64_t(j) * ne + e0 + k];
+}
+
+template<int TS>
+__device__ __forceinline__ void
+unbitshuffle_unit(const uint8_t* sb, uint8_t* db, uint32_t ts, uint32_t ne, uint32_t q)
+{
+    constexpr uint32_t E = kBitUnitElems<TS>;
+    constexpr uint32_t GB = E / 8; // bytes of every bit row a unit takes
+    const uint32_t row = ne / 8;
+    const uint32_t g0 = q * GB;
+    const uint32_t cnt = row - g0 < GB ? row - g0 : GB;
+    if constexpr (TS == 1 || TS == 2 || TS == 4 || TS == 8) {
+        if (cnt == GB) {
+            uint64_t rows[8 * TS];
+#pragma unroll
+            for (int r = 0; r < 8 * TS; ++r) {
+                const uint8_t* p = sb + uint64_t(r) * row + g0;
+                if constexpr (GB == 8)
+                    rows[r] = *reinterpret_cast<const u64_u*>(p);
+                else
+                    rows[r] = *reinterpret_cast<const u32_u*>(p);
+            }
+            uint8_t e[E * TS];
+#pragma unroll
+            for (int j = 0; j < TS; ++j)
+#pragma unroll
+                for (uint32_t g = 0; g < GB; ++g) {
+                    // byte b = bit row j * 8 + b of this group: bit 8b + k is
+                    // bit b of byte j of element 8g + k; the transpose turns
+                    // byte k into that element's byte
+                    uint64_t x = 0;
+#pragma unroll
+                    for (int b = 0; b < 8; ++b)
+                        x |= ((rows[j * 8 + b] >> (8 * g)) & 0xFFull) << (8 * b);
+                    x = trans_bit_8x8(x);
+#pragma unroll
+                    for (int k = 0; k < 8; ++k)
+                        e[(g * 8 + k) * TS + j] = uint8_t(x >> (8 * k));
+                }
+            u32x4 v[E * TS / 16];
+            __builtin_memcpy(v, e, sizeof(e));
+            auto* d = reinterpret_cast<u32x4_u*>(db + uint64_t(g0) * 8 * TS);
+#pragma unroll
+            for (uint32_t i = 0; i < E * TS / 16; ++i)
+                d[i] = v[i];
+            return;
+        }
+    }
+    for (uint32_t g = 0; g < cnt; ++g)
+        for (uint32_t k = 0; k < 8; ++k) {
+            const uint32_t m = g0 + g;
+            for (uint32_t j = 0; j < ts; ++j) {
+                uint32_t v = 0;
+                for (uint32_t b = 0; b < 8; ++b)
+                    v |= ((uint32_t(sb[uint64_t(j * 8 + b) * row + m]) >> k) & 1u) << b;
+                db[uint64_t(m * 8 + k) * ts + j] = uint8_t(v);
+            }
+        }
+}
+
+template<int TS>
+__global__ __launch_bounds__(256) void
+blosc_unfilter_kernel(UnfilterCall c)
+{
+    const uint32_t ts = TS ? uint32_t(TS) : c.ts;
+    const uint32_t k = c.k0 + blockIdx.x / c.blocks_per;
+    const uint32_t t0 = (blockIdx.x % c.blocks_per) * 256 + threadIdx.x;
+    const uint32_t T = c.blocks_per * 256;
+    uint32_t mode = c.mode, bs = c.bs;
+    if (c.meta) {
+        mode = c.meta[2 * uint64_t(k)];
+        bs = c.meta[2 * uint64_t(k) + 1];
+        if (mode == kUnfilterSkip || bs == 0)
+            return;
+    }
+    const uint8_t* s = c.src + uint64_t(k) * c.src_stride;
+    uint8_t* d = c.dst + uint64_t(k) * c.dst_stride;
+    const uint32_t full = c.nbytes / bs, left = c.nbytes % bs;
+    // what a block of `bsz` bytes went through, and its units
+    auto kind_of = [&](uint32_t bsz) {
+        return mode == kUnfilterCopy ? uint32_t(blosc::kNoFilter) : blosc::block_filter(mode, ts, bsz);
+    };
+    auto units_of = [&](uint32_t bsz, uint32_t kind) {
+        const uint32_t n = kind == blosc::kNoFilter ? (bsz + 15) / 16
+                                                    : (bsz / ts + (kind == blosc::kByteShuffle ? 7u : kBitUnitElems<TS> - 1)) /
+                                                        (kind == blosc::kByteShuffle ? 8u : kBitUnitElems<TS>);
+        return n ? n : 1u;
+    };
+    const uint32_t kind_full = kind_of(bs), upb = units_of(bs, kind_full);
+    const uint32_t kind_left = kind_of(left), upl = left ? units_of(left, kind_left) : 0u;
+    const uint64_t units = uint64_t(full) * upb + upl;
+    for (uint64_t u = t0; u < units; u += T) {
+        uint32_t b, q, bsz, kind, n_units;
+        if (u < uint64_t(full) * upb) {
+            b = uint32_t(u / upb);
+            q = uint32_t(u % upb);
+            bsz = bs;
+            kind = kind_full;
+            n_units = upb;
+        } else {
+            b = full;
+            q = uint32_t(u - uint64_t(full) * upb);
+            bsz = left;
+            kind = kind_left;
+            n_units = upl;
+        }
+        const uint8_t* sb = s + uint64_t(b) * bs;
+        uint8_t* db = d + uint64_t(b) * bs;
+        if (kind == blosc::kNoFilter) {
+            const uint32_t o = q * 16;
+            if (bsz - o >= 16) {
+                *reinterpret_cast<u32x4_u*>(db + o) = *reinterpret_cast<const u32x4_u*>(sb + o);
+            } else {
+                for (uint32_t i = o; i < bsz; ++i)
+                    db[i] = sb[i];
+            }
+            continue;
+        }
+        const uint32_t ne = bsz / ts;
+        if (kind == blosc::kByteShuffle)
+            unshuffle_unit<TS>(sb, db, ts, ne, q);
+        else
+            unbitshuffle_unit<TS>(sb, db, ts, ne, q);
+        if (q == n_units - 1) // the blocksize % typesize tail
+            for (uint32_t o = ne * ts; o < bsz; ++o)
+                db[o] = sb[o];
+    }
+}
+
+// `per` workgroups for each of n buffers, in launches of fewer than 2^31
+// workgroups: launch(k0, nk)
+template<typename L>
+hipError_t
+for_buffer_slices(uint32_t n, uint32_t per, L&& launch)
+{
+    const uint32_t cap = 0x7FFFFFFFu / per;
+    if (cap == 0)
+        return hipErrorInvalidValue;
+    for (uint64_t k0 = 0; k0 < n; k0 += cap) {
+        launch(uint32_t(k0), uint32_t(n - k0 < cap ? n - k0 : cap));
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
+}
+
+} // namespace
+
+hipError_t
+launch_blosc_unfilter(int shuffle, uint32_t typesize, uint32_t blocksize, const void* src,
+                      uint64_t src_stride, uint32_t nbytes, uint32_t n_buffers, void* dst,
+                      uint64_t dst_stride, const uint32_t* meta, hipStream_t stream)
+{
+    if (typesize == 0 || (!meta && blocksize == 0) || shuffle < 0 || shuffle > 2 ||
+        n_buffers == 0 || nbytes > 0x7FFFFFFFu)
+        return hipErrorInvalidValue;
+    if (nbytes == 0)
+        return hipSuccess;
+    // a thread for every 8 elements (or 16 bytes): larger units stride less
+    const uint32_t unit = typesize > 2 ? 8 * typesize : 16;
+    const uint64_t threads = (uint64_t(nbytes) + unit - 1) / unit;
+    UnfilterCall c{ static_cast<const uint8_t*>(src), src_stride, static_cast<uint8_t*>(dst),
+                    dst_stride, meta, shuffle ? uint32_t(shuffle) : kUnfilterCopy, blocksize,
+                    typesize, nbytes, uint32_t((threads + 255) / 256), 0 };
+    return for_buffer_slices(n_buffers, c.blocks_per, [&](uint32_t k0, uint32_t nk) {
+        c.k0 = k0;
+        const dim3 grid(nk * c.blocks_per), block(256);
+        if (launch_log_on())
+            launch_log_record("family=unfilter dtype=%u method=%d n_out=1 grid=%u block=256 "
+                              "form=%s per_frame=%d",
+                              typesize, shuffle, grid.x,
+                              (typesize == 1 || typesize == 2 || typesize == 4 || typesize == 8 ||
+                               typesize == 16)
+                                ? "vec"
+                                : "generic",
+                              meta ? 1 : 0);
+        switch (typesize) {
+            case 1: hipLaunchKernelGGL(blosc_unfilter_kernel<1>, grid, block, 0, stream, c); break;
+            case 2: hipLaunchKernelGGL(blosc_unfilter_kernel<2>, grid, block, 0, stream, c); break;
+            case 4: hipLaunchKernelGGL(blosc_unfilter_kernel<4>, grid, block, 0, stream, c); break;
+            case 8: hipLaunchKernelGGL(blosc_unfilter_kernel<8>, grid, block, 0, stream, c); break;
+            case 16: hipLaunchKernelGGL(blosc_unfilter_kernel<16>, grid, block, 0, stream, c); break;
+            default: hipLaunchKernelGGL(blosc_unfilter_kernel<0>, grid, block, 0, stream, c); break;
+        }
+    });
+}
+
+hipError_t
+launch_lz4_decode_blocks(const void* comp, const uint64_t* comp_offsets, const uint32_t* csize,
+                         void* out, const uint64_t* out_offsets, const uint32_t* cap, int32_t* results,
+                         uint32_t n_splits, hipStream_t stream)
+{
+    if (n_splits == 0 || n_splits >= (1u << 31))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lz4_decode_blocks_kernel, dim3(n_splits), dim3(64), 0, stream,
+                       static_cast<const uint8_t*>(comp), comp_offsets, csize,
+                       static_cast<uint8_t*>(out), out_offsets, cap, results);
+    return hipGetLastError();
+}
+
+hipError_t
+launch_blosc_decode(const BloscDecodeCall& call, uint32_t n_frames, hipStream_t stream)
+{
+    if (n_frames == 0 || call.nbytes == 0 || call.typesize == 0 || call.nbytes > blosc::kMaxBuffer)
+        return hipErrorInvalidValue;
+    if (const hipError_t e = hipMemsetAsync(call.status, 0, sizeof(uint32_t) * uint64_t(n_frames), stream);
+        e != hipSuccess)
+        return e;
+    // a wave for every 8 KiB of a chunk, 32 at the most: c-blosc's splits are
+    // 16 KiB and up, and a wave without a split ends at once
+    const uint32_t waves = call.nbytes / 8192 < 1 ? 1u : (call.nbytes / 8192 > 32 ? 32u : call.nbytes / 8192);
+    if (const hipError_t e = for_buffer_slices(n_frames, waves, [&](uint32_t k0, uint32_t nk) {
+            if (launch_log_on())
+                launch_log_record("family=blosc_decode dtype=%u grid=%u block=64 waves=%u "
+                                  "frames=%u shard=%d",
+                                  call.typesize, nk * waves, waves, nk, call.table ? 1 : 0);
+            hipLaunchKernelGGL(blosc_decode_kernel, dim3(nk * waves), dim3(64), 0, stream, call,
+                               k0, waves);
+        });
+        e != hipSuccess)
+        return e;
+    return launch_blosc_unfilter(1, call.typesize > 255 ? 1u : call.typesize, 0, call.scratch,
+                                 call.nbytes, call.nbytes, n_frames, call.dst, call.dst_stride,
+                                 call.meta, stream);
 }
 
 } // namespace aqz

@@ -196,6 +196,132 @@ int aqz_debug_lz4_splits_device(aqz_blosc_ctx* ctx,
                                 void* hip_stream,
                                 uint32_t flags);
 
+/*
+ * Reading the frames back on the device: blosc_d for LZ4
+ * frames, c-blosc's or the ones above.  csrc/blosc_decode.hh states the
+ * frame walk, the LZ4 block decoder and the unfilter serially for host and
+ * device; one wave decodes one split.
+ *
+ * Every frame gets a status, the first of these that applies:
+ */
+#define AQZ_BLOSC_FRAME_OK 0u          /* decoded */
+#define AQZ_BLOSC_FRAME_ABSENT 1u      /* a shard table's sentinel pair: the chunk reads as zeros */
+#define AQZ_BLOSC_FRAME_BAD_HEADER 2u  /* fewer than 16 bytes; version not 2; typesize or nbytes  \
+                                          not the caller's; blocksize 0, above nbytes, or not a   \
+                                          typesize multiple in a split frame; cbytes not the      \
+                                          frame's extent (nbytes + 16 for a memcpy frame) */
+#define AQZ_BLOSC_FRAME_UNSUPPORTED 3u /* not a memcpy frame, and its codec is not LZ4 (version 1) */
+#define AQZ_BLOSC_FRAME_CORRUPT 4u     /* block starts, split sizes or an LZ4 stream out of       \
+                                          bounds; a split that decodes to another length; a shard \
+                                          table pair outside the shard's bytes */
+/* A frame that is neither OK nor ABSENT leaves its chunk's bytes unspecified;
+ * nothing outside the chunk's nbytes is written, nothing outside the frame's
+ * extent is read. */
+
+/* The 16 header bytes of a frame and what they say about it. */
+typedef struct
+{
+    uint32_t status; /* AQZ_BLOSC_FRAME_*, as far as the header and the block starts decide it */
+    uint8_t version, versionlz, flags, typesize;
+    uint32_t nbytes, blocksize, cbytes;
+    uint32_t memcpyed; /* flags & 0x2: the chunk itself follows the header */
+    uint32_t shuffle;  /* AQZ_BLOSC_NOSHUFFLE / SHUFFLE / BITSHUFFLE the blocks went through */
+    uint32_t nsplits;  /* streams of a full block: typesize or 1 */
+    uint32_t nblocks;
+} aqz_blosc_frame_header;
+
+/* Host only, no GPU involved: parses frame[0, extent) against the caller's
+ * typesize and nbytes (0: whatever the header says).  AQZ_INVALID_ARGUMENT
+ * for a null pointer; a bad frame is reported in out->status, not as an
+ * error. */
+int aqz_blosc_frame_info(const void* frame,
+                         size_t extent,
+                         uint32_t typesize,
+                         size_t nbytes,
+                         aqz_blosc_frame_header* out);
+
+/*
+ * blosc_d's unfilter step, the inverse of aqz_blosc_filter_device with the
+ * same block rules: `n_buffers` buffers of `nbytes` each (at most 2^31 - 1),
+ * back to back, every `blocksize` block byte-unshuffled (shuffle 1, typesize >
+ * 1), bit-unshuffled (2, a whole element and a multiple of 8 of them) or
+ * copied, the blocksize % typesize tail copied.  Not in place.  Asynchronous
+ * on `hip_stream`.
+ */
+int aqz_blosc_unfilter_device(int shuffle,
+                              uint32_t typesize,
+                              uint32_t blocksize,
+                              const void* device_src,
+                              size_t nbytes,
+                              uint32_t n_buffers,
+                              void* device_dst,
+                              void* hip_stream);
+
+/*
+ * `n_frames` LZ4 frames back into chunks of `nbytes` (typesize > 255 counts
+ * as 1, as for the writers).  Frame k lies at device_frames + k * frame_stride
+ * and is device_frame_bytes[k] long, the uint32 table
+ * aqz_blosc_lz4_frames_device writes (a size above frame_stride counts as
+ * frame_stride); NULL: the size is the header's cbytes, which must fit into
+ * frame_stride.  Chunk k goes to device_dst + k * dst_stride, its status to
+ * device_status[k].
+ *
+ * Header fields are read on the device only; the launch geometry follows
+ * from typesize, nbytes and n_frames.  Everything is queued on `hip_stream`;
+ * the call never synchronises.  The filtered chunks pass through scratch
+ * inside ctx: only a call that needs more of it than any before frees and
+ * reallocates, which waits for the device.  Frames without a filter and
+ * memcpy frames are written straight to device_dst.
+ *
+ * AQZ_INVALID_ARGUMENT before anything is queued: a null ctx or pointer
+ * (device_frame_bytes may be NULL), typesize, nbytes or n_frames 0,
+ * dst_stride < nbytes, nbytes above BLOSC_MAX_BUFFERSIZE (2^31 - 17).
+ */
+int aqz_blosc_lz4_decompress_device(aqz_blosc_ctx* ctx,
+                                    uint32_t typesize,
+                                    size_t nbytes,
+                                    const void* device_frames,
+                                    size_t frame_stride,
+                                    const uint32_t* device_frame_bytes,
+                                    uint32_t n_frames,
+                                    void* device_dst,
+                                    size_t dst_stride,
+                                    uint32_t* device_status,
+                                    void* hip_stream);
+
+/* Test seams, host only.  lz4::decode_block of csrc/blosc_decode.hh:
+ * LZ4_decompress_safe(src, dst, n, cap), the decoded size or a negative
+ * error (-1 empty input, -2 truncated, -3 / -4 literals past the input / the
+ * output, -5 offset 0, -6 offset before the output, -7 match past the output,
+ * -8 the block ends in a match; -100 for a bad argument). */
+int aqz_debug_lz4_decode_host(const void* src, size_t n, void* dst, size_t cap);
+
+/* A whole frame through the walker, the serial decoder and a host unfilter:
+ * frame[0, extent) into dst[0, nbytes), *status as the device call gives it. */
+int aqz_debug_blosc_decode_host(const void* frame,
+                                size_t extent,
+                                uint32_t typesize,
+                                size_t nbytes,
+                                void* dst,
+                                uint32_t* status);
+
+/* The device decoder on bare LZ4 blocks, without frame or unfilter: block k
+ * is device_comp[comp_offsets[k], + csize[k]), one wave decodes it into
+ * device_out + out_offsets[k] with capacity device_cap[k], results[k] is the decoded
+ * size or the error aqz_debug_lz4_decode_host names.  All arrays are device
+ * memory; queued on `hip_stream`, no synchronisation; `ctx` names the device
+ * only. */
+int aqz_debug_lz4_decode_blocks_device(aqz_blosc_ctx* ctx,
+                                       const void* device_comp,
+                                       const uint64_t* device_comp_offsets,
+                                       const uint32_t* device_csize,
+                                       void* device_out,
+                                       const uint64_t* device_out_offsets,
+                                       const uint32_t* device_cap,
+                                       int32_t* device_results,
+                                       uint32_t n_blocks,
+                                       void* hip_stream);
+
 /* Which LZ4 and zstd libraries the frame writer loaded, with versions
  * ("" entries for a codec that failed to load).  $AQZ_LZ4_LIB and
  * $AQZ_ZSTD_LIB name them explicitly. */

@@ -19,6 +19,7 @@
 #ifndef AQZ_SHARD_H
 #define AQZ_SHARD_H
 
+#include "aqz_blosc.h"
 #include "aqz_downsampler.h"
 
 #ifdef __cplusplus
@@ -210,6 +211,47 @@ int aqz_zarr_shard_chunk_has_data_device(const uint8_t* device_tile_nonzero,
                                          const uint32_t* host_frame_chunk_base,
                                          uint8_t* device_has_data,
                                          void* hip_stream);
+
+/*
+ * A shard's chunks back out of its bytes, on the device: the read side of
+ * append_layer_device + tables_device for blosc LZ4 chunks
+ * (aqz_blosc_lz4_decompress_device with the frames found through an index
+ * table; statuses AQZ_BLOSC_FRAME_* of aqz_blosc.h).
+ *
+ * `device_table` is one shard's index table exactly as
+ * aqz_zarr_shard_set_tables_device writes it: n_chunks (offset, extent)
+ * uint64 pairs at any byte alignment (tables lie 16 * n + 4 bytes apart); the
+ * CRC behind them is not read (aqz_crc32c_device checks
+ * it).  The offsets are file offsets; device_shard_bytes holds the
+ * shard_bytes bytes of the file from base_file_offset on, so chunk i's frame
+ * lies at device_shard_bytes + offset - base_file_offset, at any byte
+ * alignment.  Chunk i is written to device_dst + i * dst_stride and its
+ * status to device_status[i]:
+ *   - the sentinel pair: ABSENT, the chunk zero-filled (the fill value of the
+ *     arrays written here);
+ *   - a pair that leaves [0, shard_bytes): CORRUPT;
+ *   - else what the frame's header and bytes give.
+ * Not the tool for an uncompressed array's shards, whose extents are nbytes
+ * and whose chunks carry no blosc header: those are BAD_HEADER here; copy
+ * them with the table instead.
+ *
+ * Queued on `hip_stream`, never synchronises; ctx scratch as for
+ * aqz_blosc_lz4_decompress_device.  AQZ_INVALID_ARGUMENT before anything is
+ * queued: a null ctx or pointer, typesize, nbytes or n_chunks 0, dst_stride <
+ * nbytes, nbytes above BLOSC_MAX_BUFFERSIZE.
+ */
+int aqz_zarr_shard_decompress_device(aqz_blosc_ctx* ctx,
+                                     uint32_t typesize,
+                                     size_t nbytes,
+                                     const void* device_shard_bytes,
+                                     size_t shard_bytes,
+                                     uint64_t base_file_offset,
+                                     const uint64_t* device_table,
+                                     uint32_t n_chunks,
+                                     void* device_dst,
+                                     size_t dst_stride,
+                                     uint32_t* device_status,
+                                     void* hip_stream);
 
 /* Test seams.  Bytes the last aqz_zarr_shard_set_append_layer on `set`
  * copied from device to host (segment table + segments). */
