@@ -69,6 +69,7 @@ EXPORTS = (
     "aqz_blosc_frame_info", "aqz_blosc_unfilter_device", "aqz_blosc_lz4_decompress_device",
     "aqz_zarr_shard_decompress_device", "aqz_debug_lz4_decode_host",
     "aqz_debug_blosc_decode_host", "aqz_debug_lz4_decode_blocks_device",
+    "aqz_chunk_frame_places", "aqz_chunk_gather_frames_device", "aqz_untile_frame_device",
 )
 
 
@@ -299,6 +300,11 @@ def lib() -> ctypes.CDLL:
     L.aqz_debug_lz4_decode_host.argtypes = [vp, sz, vp, sz]
     L.aqz_debug_blosc_decode_host.argtypes = [vp, sz, u32, sz, vp, ctypes.POINTER(u32)]
     L.aqz_debug_lz4_decode_blocks_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]
+    L.aqz_chunk_frame_places.argtypes = [ctypes.POINTER(Dimension), u32, u32, ctypes.c_uint64,
+                                         u32, vp, vp, u64p, ctypes.POINTER(u32)]
+    L.aqz_chunk_gather_frames_device.argtypes = [i32, u32, u32, u32, u32, vp, sz, u32, vp, u32,
+                                                 vp, vp, u32, vp, sz, vp, vp]
+    L.aqz_untile_frame_device.argtypes = [i32, vp, u32, u32, u32, u32, vp, vp]
     _lib = L
     return L
 
@@ -1075,6 +1081,56 @@ def zarr_shard_chunk_has_data_device(device_tile_nonzero: int, n_frames: int, n_
     base = (ctypes.c_uint32 * max(n_frames, 1))(*[int(b) for b in frame_chunk_base])
     _raise_if(lib().aqz_zarr_shard_chunk_has_data_device(
         device_tile_nonzero, n_frames, n_tiles, flag_slots, base, device_has_data,
+        ctypes.c_void_p(stream) if stream else None))
+
+
+CHUNK_SLOT_ABSENT = 0xFFFFFFFF  # AQZ_CHUNK_SLOT_ABSENT, aqz_shard.h
+CHUNK_GATHER_FRAMES = 64  # kGatherFrames, csrc/gather_kernels.hh
+
+
+def chunk_frame_places(dims, bytes_per_px: int, first_frame: int, n_frames: int):
+    """aqz_chunk_frame_places: (frame_chunk_base uint32[n_frames],
+    frame_internal_offset_bytes uint64[n_frames], chunk_bytes,
+    chunks_per_layer) for storage-order `dims` = [(type, array_size,
+    chunk_size, shard_size_chunks), ...].  Host only, no GPU involved."""
+    base = np.zeros(max(n_frames, 1), np.uint32)
+    internal = np.zeros(max(n_frames, 1), np.uint64)
+    cb, cpl = ctypes.c_uint64(), ctypes.c_uint32()
+    rc = lib().aqz_chunk_frame_places(_dim_array(dims) if dims else None, len(dims),
+                                      bytes_per_px, first_frame, n_frames, base.ctypes.data,
+                                      internal.ctypes.data, ctypes.byref(cb), ctypes.byref(cpl))
+    if rc:
+        raise AqzError(rc, "chunk_frame_places: bad dimensions, or a chunk index past 2^32 - 2")
+    return base[:n_frames], internal[:n_frames], cb.value, cpl.value
+
+
+def chunk_gather_frames_device(dtype, width: int, height: int, tile_rows: int, tile_cols: int,
+                               device_chunks: int, chunk_stride_bytes: int, n_slots: int,
+                               device_chunk_slot: int, n_chunks: int, frame_chunk_base,
+                               frame_internal_offset_bytes, device_frames: int,
+                               frame_stride_bytes: int, device_bad_slot: int = 0,
+                               stream: int = 0):
+    """aqz_chunk_gather_frames_device (asynchronous on `stream`): one frame per
+    entry of `frame_chunk_base`; `device_chunk_slot` 0 is the identity table."""
+    base = np.ascontiguousarray(frame_chunk_base, np.uint32)
+    internal = np.ascontiguousarray(frame_internal_offset_bytes, np.uint64)
+    if base.shape != internal.shape or base.ndim != 1:
+        raise ValueError("one chunk base and one internal offset per frame")
+    _raise_if(lib().aqz_chunk_gather_frames_device(
+        dtype if isinstance(dtype, int) else dtype_code(dtype), width, height, tile_rows,
+        tile_cols, device_chunks or None, chunk_stride_bytes, n_slots,
+        device_chunk_slot or None, n_chunks, base.ctypes.data, internal.ctypes.data, len(base),
+        device_frames or None, frame_stride_bytes, device_bad_slot or None,
+        ctypes.c_void_p(stream) if stream else None))
+
+
+def untile_frame_device(dtype, device_tiles: int, width: int, height: int, tile_rows: int,
+                        tile_cols: int, device_frame: int, stream: int = 0):
+    """aqz_untile_frame_device (asynchronous on `stream`): the inverse of
+    tile_frame_device."""
+    _raise_if(lib().aqz_untile_frame_device(
+        dtype if isinstance(dtype, int) else dtype_code(dtype), device_tiles or None, width,
+        height, tile_rows, tile_cols, device_frame or None,
         ctypes.c_void_p(stream) if stream else None))
 
 

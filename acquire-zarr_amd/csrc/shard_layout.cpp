@@ -8,6 +8,7 @@
 #include "aqz_shard.h"
 
 #include <cstdint>
+#include <vector>
 
 namespace {
 
@@ -87,6 +88,66 @@ aqz_zarr_shard_layout(const aqz_dimension* dims, uint32_t ndims, uint32_t layer_
                 break;
             lattice[i] = 0;
         }
+    }
+    return AQZ_OK;
+}
+
+// array.dimensions.cpp:232-314 (chunk_lattice_index, tile_group_offset,
+// chunk_internal_offset) with the sum of aqz_chunk_frame_offsets kept in its
+// parts: offsets[k] == base[k] * chunk_bytes + internal[k].
+extern "C" int
+aqz_chunk_frame_places(const aqz_dimension* dims, uint32_t ndims, uint32_t bytes_per_px,
+                       uint64_t first_frame, uint32_t n_frames, uint32_t* frame_chunk_base,
+                       uint64_t* frame_internal_offset_bytes, uint64_t* chunk_bytes,
+                       uint32_t* chunks_per_layer)
+{
+    if (!dims || ndims < 3 || bytes_per_px == 0 ||
+        (n_frames && (!frame_chunk_base || !frame_internal_offset_bytes)))
+        return AQZ_INVALID_ARGUMENT;
+    for (uint32_t i = 0; i < ndims; ++i)
+        if (dims[i].chunk_size_px == 0 || (i > 0 && dims[i].array_size_px == 0))
+            return AQZ_INVALID_ARGUMENT;
+    const uint32_t nd = ndims;
+    // chunk-lattice strides of every dimension; strides[0] is a layer's chunks
+    std::vector<uint64_t> strides(nd, 1);
+    for (uint32_t i = nd - 1; i > 0; --i)
+        strides[i - 1] = strides[i] * ceil_div(dims[i].array_size_px, dims[i].chunk_size_px);
+    const uint64_t per_layer = strides[0];
+    const uint64_t n_tiles = strides[nd - 3]; // tiles of one frame
+    uint64_t per_chunk = bytes_per_px;
+    for (uint32_t i = 0; i < nd; ++i)
+        per_chunk *= dims[i].chunk_size_px;
+    const uint64_t tile_bytes =
+      uint64_t(bytes_per_px) * dims[nd - 1].chunk_size_px * dims[nd - 2].chunk_size_px;
+    uint64_t layer_frames = dims[0].chunk_size_px;
+    for (uint32_t i = 1; i + 2 < nd; ++i)
+        layer_frames *= dims[i].array_size_px;
+    const uint64_t layer0 = first_frame / layer_frames;
+    for (uint32_t k = 0; k < n_frames; ++k) {
+        const uint64_t fid = first_frame + k;
+        // walk the frame dimensions from the innermost: `rest` is the frame id
+        // in units of dimension i, `inner` the frames of one chunk below it
+        uint64_t rest = fid, group = 0, internal = 0, inner = 1;
+        for (uint32_t i = nd - 3; i > 0; --i) {
+            const uint64_t idx = rest % dims[i].array_size_px;
+            rest /= dims[i].array_size_px;
+            group += idx / dims[i].chunk_size_px * strides[i];
+            internal += idx % dims[i].chunk_size_px * inner;
+            inner *= dims[i].chunk_size_px;
+        }
+        internal += rest % dims[0].chunk_size_px * inner;
+        const uint64_t base = (fid / layer_frames - layer0) * per_layer + group;
+        if (base + n_tiles >= UINT32_MAX) // UINT32_MAX is AQZ_CHUNK_SLOT_ABSENT
+            return AQZ_OVERFLOW;
+        frame_chunk_base[k] = uint32_t(base);
+        frame_internal_offset_bytes[k] = internal * tile_bytes;
+    }
+    if (chunk_bytes)
+        *chunk_bytes = per_chunk;
+    if (chunks_per_layer) {
+        if (per_layer >= UINT32_MAX)
+            return AQZ_OVERFLOW;
+        *chunks_per_layer = uint32_t(per_layer);
     }
     return AQZ_OK;
 }

@@ -4,6 +4,8 @@
 #include "aqz_shard.h"
 #include "abi_guard.hh"
 #include "codec_kernels.hh"
+#include "ds_plan.hh"
+#include "gather_kernels.hh"
 #include "shard_kernels.hh"
 
 #include <hip/hip_runtime.h>
@@ -437,6 +439,125 @@ aqz_zarr_shard_chunk_has_data_device(const uint8_t* device_tile_nonzero, uint32_
                                                         device_has_data,
                                                         static_cast<hipStream_t>(hip_stream)),
                           "chunk flags");
+    } catch (...) {
+        return ABI_GUARD_FAIL(nullptr);
+    }
+}
+
+// Every refusal of the gather, then the launcher: shared by the batch call and
+// the single-frame inverse.
+static int
+gather_frames(const char* who, int dtype, uint32_t width, uint32_t height, uint32_t tile_rows,
+              uint32_t tile_cols, const void* device_chunks, size_t chunk_stride_bytes,
+              uint32_t n_slots, const uint32_t* device_chunk_slot, uint32_t n_chunks,
+              const uint32_t* host_base, const uint64_t* host_internal, uint32_t n_frames,
+              void* device_frames, size_t frame_stride_bytes, uint32_t* device_bad_slot,
+              void* hip_stream)
+{
+    auto refuse = [who](const char* what) { return invalid((std::string(who) + ": " + what).c_str()); };
+    if (!device_chunks || !host_base || !host_internal || !device_frames)
+        return refuse("null pointer");
+    if (!aqz::dtype_valid(dtype))
+        return refuse("bad dtype");
+    if (width == 0 || height == 0 || tile_rows == 0 || tile_cols == 0 || n_slots == 0 ||
+        n_chunks == 0 || n_frames == 0 || chunk_stride_bytes == 0 || frame_stride_bytes == 0)
+        return refuse("a zero extent, tile side, count or stride");
+    const uint64_t bpp = aqz::dtype_bytes(dtype);
+    uint32_t lg = 0;
+    while ((1u << lg) < bpp)
+        ++lg;
+    const uint64_t tile_elems = uint64_t(tile_rows) * tile_cols;
+    const uint64_t ntx = (uint64_t(width) + tile_cols - 1) / tile_cols;
+    const uint64_t n_tiles = ntx * ((uint64_t(height) + tile_rows - 1) / tile_rows);
+    if (tile_elems >= (1ull << 31) || n_tiles >= (1ull << 31))
+        return refuse("a tile of 2^31 elements or more, or 2^31 tiles or more");
+    if (chunk_stride_bytes % bpp || frame_stride_bytes % bpp)
+        return refuse("a stride that is not a multiple of the pixel size");
+    if (reinterpret_cast<uintptr_t>(device_chunks) % bpp ||
+        reinterpret_cast<uintptr_t>(device_frames) % bpp)
+        return refuse("a buffer that is not aligned to the pixel size");
+    const uint64_t n_px = uint64_t(width) * height;
+    if (n_px > UINT64_MAX / bpp || frame_stride_bytes < n_px * bpp)
+        return refuse("frame_stride_bytes below width * height * pixel size");
+    if (!device_chunk_slot && n_chunks != n_slots)
+        return refuse("no slot table, and n_chunks differs from n_slots");
+    const uint64_t tile_bytes = tile_elems * bpp;
+    for (uint32_t k = 0; k < n_frames; ++k) {
+        if (host_internal[k] % bpp)
+            return refuse("an internal offset that is not a multiple of the pixel size");
+        if (host_internal[k] > chunk_stride_bytes ||
+            tile_bytes > chunk_stride_bytes - host_internal[k])
+            return refuse("an internal offset whose tile ends past chunk_stride_bytes");
+        if (uint64_t(host_base[k]) + n_tiles > n_chunks)
+            return refuse("a frame's chunks end past n_chunks");
+    }
+    aqz::GatherArgs a{};
+    a.chunks = static_cast<const uint8_t*>(device_chunks);
+    a.chunk_stride = chunk_stride_bytes;
+    a.slot = device_chunk_slot;
+    a.n_slots = n_slots;
+    a.bpp_log2 = lg;
+    a.W = width;
+    a.H = height;
+    a.tile_rows = tile_rows;
+    a.tile_cols = tile_cols;
+    a.n_tiles_x = uint32_t(ntx);
+    a.frames = static_cast<uint8_t*>(device_frames);
+    a.frame_stride = frame_stride_bytes;
+    a.bad_slot = device_bad_slot;
+    const hipError_t e = aqz::launch_chunk_gather(a, host_base, host_internal, n_frames,
+                                                  static_cast<hipStream_t>(hip_stream));
+    if (e == hipErrorInvalidValue)
+        return refuse("a launch grid of 2^31 workgroups or more");
+    return hip_status(e, who);
+}
+
+int
+aqz_chunk_gather_frames_device(int dtype, uint32_t width, uint32_t height, uint32_t tile_rows,
+                               uint32_t tile_cols, const void* device_chunks,
+                               size_t chunk_stride_bytes, uint32_t n_slots,
+                               const uint32_t* device_chunk_slot, uint32_t n_chunks,
+                               const uint32_t* host_frame_chunk_base,
+                               const uint64_t* host_frame_internal_offset_bytes,
+                               uint32_t n_frames, void* device_frames, size_t frame_stride_bytes,
+                               uint32_t* device_bad_slot, void* hip_stream)
+{
+    try {
+        return gather_frames("chunk_gather_frames_device", dtype, width, height, tile_rows,
+                             tile_cols, device_chunks, chunk_stride_bytes, n_slots,
+                             device_chunk_slot, n_chunks, host_frame_chunk_base,
+                             host_frame_internal_offset_bytes, n_frames, device_frames,
+                             frame_stride_bytes, device_bad_slot, hip_stream);
+    } catch (...) {
+        return ABI_GUARD_FAIL(nullptr);
+    }
+}
+
+int
+aqz_untile_frame_device(int dtype, const void* device_tiles, uint32_t width, uint32_t height,
+                        uint32_t tile_rows, uint32_t tile_cols, void* device_frame,
+                        void* hip_stream)
+{
+    try {
+        const char* who = "untile_frame_device";
+        if (!aqz::dtype_valid(dtype) || width == 0 || height == 0 || tile_rows == 0 ||
+            tile_cols == 0)
+            return invalid("untile_frame_device: bad dtype or a zero extent or tile side");
+        const uint64_t bpp = aqz::dtype_bytes(dtype);
+        const uint64_t tile_elems = uint64_t(tile_rows) * tile_cols;
+        const uint64_t n_tiles = ((uint64_t(width) + tile_cols - 1) / tile_cols) *
+                                 ((uint64_t(height) + tile_rows - 1) / tile_rows);
+        const uint64_t n_px = uint64_t(width) * height;
+        if (tile_elems >= (1ull << 31) || n_tiles >= (1ull << 31) || n_px > UINT64_MAX / bpp)
+            return invalid("untile_frame_device: a tile of 2^31 elements or more, 2^31 tiles or "
+                           "more, or a frame past the address space");
+        // one frame, tiles back to back: slot t is tile t
+        const uint32_t base = 0;
+        const uint64_t internal = 0;
+        return gather_frames(who, dtype, width, height, tile_rows, tile_cols, device_tiles,
+                             size_t(tile_elems * bpp), uint32_t(n_tiles), nullptr,
+                             uint32_t(n_tiles), &base, &internal, 1, device_frame,
+                             size_t(n_px * bpp), nullptr, hip_stream);
     } catch (...) {
         return ABI_GUARD_FAIL(nullptr);
     }

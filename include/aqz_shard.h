@@ -253,6 +253,113 @@ int aqz_zarr_shard_decompress_device(aqz_blosc_ctx* ctx,
                                      uint32_t* device_status,
                                      void* hip_stream);
 
+/*
+ * The next step of a read: the decoded chunks are still tiles.
+ * aqz_chunk_frame_places says where each frame's tiles lie among them and
+ * aqz_chunk_gather_frames_device writes the frames out row-major
+ * (DESIGN.md §12.14).
+ *
+ * Host only, no GPU involved (csrc/shard_layout.cpp).  aqz_chunk_frame_offsets
+ * with its sum kept in parts, for the same arguments and with the same
+ * refusals: for frame k = 0 .. n_frames - 1 of a batch that starts at frame
+ * `first_frame` of the array,
+ *   frame_chunk_base[k]            = (layer(k) - layer(first_frame))
+ *                                    * chunks_per_layer + tile_group_offset(k)
+ *   frame_internal_offset_bytes[k] = chunk_internal_offset(k)
+ * so tile t of frame k lies in chunk frame_chunk_base[k] + t of the batch's
+ * layers, at that offset, and
+ *   offsets[k] == frame_chunk_base[k] * chunk_bytes + frame_internal_offset_bytes[k]
+ * with aqz_chunk_frame_offsets' offsets.  chunk_bytes and chunks_per_layer may
+ * be NULL.  AQZ_OVERFLOW: a base plus the frame's tile count would reach
+ * UINT32_MAX (AQZ_CHUNK_SLOT_ABSENT), or chunks_per_layer would.
+ */
+int aqz_chunk_frame_places(const aqz_dimension* dims,
+                           uint32_t ndims,
+                           uint32_t bytes_per_px,
+                           uint64_t first_frame,
+                           uint32_t n_frames,
+                           uint32_t* frame_chunk_base,
+                           uint64_t* frame_internal_offset_bytes,
+                           uint64_t* chunk_bytes,
+                           uint32_t* chunks_per_layer);
+
+/* A chunk no buffer holds: it reads as zeros, the fill value, as
+ * AQZ_BLOSC_FRAME_ABSENT does. */
+#define AQZ_CHUNK_SLOT_ABSENT UINT32_MAX
+
+/*
+ * Chunk buffers back into row-major frames, on the device: the inverse of the
+ * chunk tiling.  Frame k (width x height pixels of `dtype`) is written at
+ * device_frames + k * frame_stride_bytes.  With n_tiles_x = ceil(width /
+ * tile_cols), its pixel (y, x) comes from chunk
+ *   c = host_frame_chunk_base[k] + (y / tile_rows) * n_tiles_x + x / tile_cols
+ * at byte
+ *   device_chunks + slot(c) * chunk_stride_bytes
+ *     + host_frame_internal_offset_bytes[k]
+ *     + ((y % tile_rows) * tile_cols + x % tile_cols) * pixel size
+ * where slot(c) = device_chunk_slot[c] (n_chunks entries, device memory), or
+ * c itself when the table is NULL (then n_chunks must equal n_slots).  The
+ * identity form reads a lattice as aqz_ds_run_device_batch_chunked[_base] and
+ * aqz_ds_run_device_volume_chunked write it.  The table form reads what
+ * aqz_zarr_shard_decompress_device wrote: with shard s decoded to
+ * dst + s * chunks_per_shard * dst_stride, slot(c) = shard_of[c] *
+ * chunks_per_shard + internal_of[c] (aqz_zarr_shard_layout).
+ *
+ * A slot AQZ_CHUNK_SLOT_ABSENT reads as zeros.  Any other slot >= n_slots
+ * reads as zeros too, nothing is loaded for it, and *device_bad_slot (if
+ * given; the caller clears it) is set to 1.
+ *
+ * Only pixels inside the frame are read: never a tile's overhang, never
+ * another frame's bytes of a chunk.  Nothing outside [k * stride, k * stride
+ * + width * height * pixel size) is written.  Everything is queued on
+ * `hip_stream`; the call never synchronises and owns no scratch.  The
+ * per-frame tables travel as kernel arguments, 64 frames a launch, so the
+ * host arrays may be freed on return.
+ *
+ * AQZ_INVALID_ARGUMENT before anything is queued: a null pointer (the slot
+ * table and device_bad_slot may be NULL); a zero extent, tile side, count or
+ * stride; a bad dtype; a tile of 2^31 elements or more, or 2^31 tiles or
+ * more; chunk_stride_bytes, an internal offset or frame_stride_bytes that is
+ * no multiple of the pixel size, or device_chunks or device_frames not
+ * aligned to it; internal[k] + tile_rows * tile_cols * pixel size >
+ * chunk_stride_bytes; base[k] + n_tiles > n_chunks; frame_stride_bytes <
+ * width * height * pixel size; a NULL table with n_chunks != n_slots; a
+ * launch grid of 2^31 workgroups or more.
+ */
+int aqz_chunk_gather_frames_device(int dtype,
+                                   uint32_t width,
+                                   uint32_t height,
+                                   uint32_t tile_rows,
+                                   uint32_t tile_cols,
+                                   const void* device_chunks,
+                                   size_t chunk_stride_bytes,
+                                   uint32_t n_slots,
+                                   const uint32_t* device_chunk_slot,
+                                   uint32_t n_chunks,
+                                   const uint32_t* host_frame_chunk_base,
+                                   const uint64_t* host_frame_internal_offset_bytes,
+                                   uint32_t n_frames,
+                                   void* device_frames,
+                                   size_t frame_stride_bytes,
+                                   uint32_t* device_bad_slot,
+                                   void* hip_stream);
+
+/*
+ * The inverse of aqz_tile_frame_device and of aqz_ds_take_frame_tiled's
+ * layout: one frame from its tiles back to back (tile t at device_tiles +
+ * t * tile_rows * tile_cols * pixel size).  The same launcher and kernels as
+ * aqz_chunk_gather_frames_device with one frame, base 0, offset 0, a stride
+ * of one tile and identity slots; its refusals apply.
+ */
+int aqz_untile_frame_device(int dtype,
+                            const void* device_tiles,
+                            uint32_t width,
+                            uint32_t height,
+                            uint32_t tile_rows,
+                            uint32_t tile_cols,
+                            void* device_frame,
+                            void* hip_stream);
+
 /* Test seams.  Bytes the last aqz_zarr_shard_set_append_layer on `set`
  * copied from device to host (segment table + segments). */
 uint64_t aqz_debug_zarr_shard_d2h_bytes(const aqz_zarr_shard_set* set);
