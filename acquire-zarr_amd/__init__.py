@@ -59,7 +59,7 @@ EXPORTS = (
     "aqz_node_add_frame", "aqz_node_take_frame", "aqz_node_flush",
     "aqz_node_run_device_batch", "aqz_node_wait_input", "aqz_ds_wait_input",
     "aqz_node_set_level_tiling", "aqz_ds_input_pending", "aqz_node_inputs_released",
-    "aqz_debug_launch_log",
+    "aqz_debug_launch_log", "aqz_debug_ds_force_per_frame_batch",
     "aqz_zarr_shard_layout", "aqz_zarr_shard_set_create", "aqz_zarr_shard_set_destroy",
     "aqz_zarr_shard_set_geometry", "aqz_zarr_shard_set_begin",
     "aqz_zarr_shard_set_append_layer_device", "aqz_zarr_shard_set_tables_device",
@@ -229,6 +229,7 @@ def lib() -> ctypes.CDLL:
                                         ctypes.POINTER(u32)]
     L.aqz_ds_last_batch_kind.argtypes = [vp]
     L.aqz_ds_last_batch_kind.restype = i32
+    L.aqz_debug_ds_force_per_frame_batch.argtypes = [vp, i32]
     L.aqz_ds_stream_tiled_runs.argtypes = [vp]
     L.aqz_ds_stream_tiled_runs.restype = ctypes.c_uint64
     L.aqz_ds_level_bytes.argtypes = [vp, u32]
@@ -477,8 +478,15 @@ class Downsampler:
     def last_batch_kind(self) -> int:
         """0 per-frame, 1 fused 2-D cascade, 2 fused volume, 3 2-D batch with
         some runs on batched single-level kernels, 4 fused 2-D cascade writing
-        chunk tiles, -1 none."""
+        chunk tiles, 5 fused volume writing chunk tiles, 6 tiled cascade with
+        its base, 7 mixed pyramid as a chain of batched runs (volume, cascade,
+        Z run), -1 none."""
         return lib().aqz_ds_last_batch_kind(self._h)
+
+    def debug_force_per_frame_batch(self, on) -> None:
+        """aqz_debug_ds_force_per_frame_batch: while on, run_device_batch
+        takes the per-frame state machine (kind 0) whatever the pyramid."""
+        self._check(lib().aqz_debug_ds_force_per_frame_batch(self._h, 1 if on else 0))
 
     def stream_tiled_runs(self) -> int:
         """Pure-XY level runs add_frame tiled in the cascade launch itself."""

@@ -150,6 +150,10 @@ AQZ_FORWARD(launch_zpair,
             (int dtype, int method, void* out, const void* earlier, const void* current,
              uint64_t n, hipStream_t stream),
             (dtype, method, out, earlier, current, n, stream))
+AQZ_FORWARD(launch_zrun,
+            (int dtype, int method, const void* src, uint64_t src_frame_elems, uint64_t elems,
+             const LevelOut* outs, int n_out, uint32_t planes, hipStream_t stream),
+            (dtype, method, src, src_frame_elems, elems, outs, n_out, planes, stream))
 AQZ_FORWARD(launch_transpose,
             (int dtype, const void* src, uint32_t rows, uint32_t cols, void* dst,
              hipStream_t stream),

@@ -12,6 +12,9 @@
 //   * volume    — both of the above fused for pyramids whose levels halve XY
 //                 and Z (3-D stacks): 2^NL planes x 2^NL rows per wave, every
 //                 level written from registers.
+//   * zrun      — zpair applied 1..3 times in one pass over a batch of whole
+//                 plane groups (levels that halve Z alone): 2^NL planes per
+//                 wave, every level written from registers.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -74,6 +77,18 @@ hipError_t launch_xy_generic(int dtype, int method, const void* src, uint64_t sr
 // either input.  16-byte vectors when all pointers are aligned, else scalar.
 hipError_t launch_zpair(int dtype, int method, void* out, const void* earlier,
                         const void* current, uint64_t n, hipStream_t stream);
+
+// 1..kMaxZLevels levels that halve Z alone, in one pass: `planes` frames of
+// `elems` elements (src_frame_elems apart) are paired down n_out times in
+// registers; level j (1-based) receives planes >> j frames at
+// outs[j-1].ptr + k * outs[j-1].frame_elems (its w and h are not read), each
+// reduce2(earlier, current) of level j-1's frames 2k and 2k+1.  Any element
+// count and element-aligned pointer; `planes` a multiple of 2^n_out.  Planned
+// by plan_zrun (ds_plan.hh), whose refusals come back as
+// hipErrorInvalidValue before anything is queued.
+hipError_t launch_zrun(int dtype, int method, const void* src, uint64_t src_frame_elems,
+                       uint64_t elems, const LevelOut* outs, int n_out, uint32_t planes,
+                       hipStream_t stream);
 
 // Chunk tiling of one W x H frame (array.cpp:507-622 / chunk.cpp:17-58):
 // transpose_frame (array.cpp:488-504): `dst` (cols x rows, row-major)

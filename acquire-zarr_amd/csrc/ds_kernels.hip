@@ -2100,6 +2100,150 @@ zpair_kernel(T* out, const T* earlier, const T* current, uint64_t n)
     }
 }
 
+// ---- Z run -------------------------------------------------------------------
+//
+// Up to kMaxZLevels consecutive levels that halve Z alone (w x h unchanged),
+// for a batch of whole plane groups: level j's plane k is
+// reduce2(earlier, current) of level j-1's planes 2k and 2k+1, each level
+// from the truncated one before it — volume_level's Z step without its XY
+// step.  A wave takes one plane group (2^NL consecutive input planes) by one
+// span of 64 lanes x kZRunVecs 16-byte vectors (ZRunPlan); a lane holds the
+// same vectors of every plane of the group, so the whole tree is in-lane.
+// Planes of any element count sit at any byte offset: loads and stores are
+// 16 bytes at byte alignment, counted from each plane's own start, and the
+// elements behind a plane's last whole vector go one to a lane from the span
+// that ends the plane.  Decimate reads the even planes only (plane 2k is
+// level 1's plane k; the odd planes feed nothing).
+struct ZRunParams
+{
+    const uint8_t* src;
+    uint64_t src_frame_elems;
+    uint64_t elems; // of one plane
+    uint32_t spans, total_units;
+    uint8_t* dst[kMaxZLevels];
+    uint64_t dst_frame_elems[kMaxZLevels];
+};
+
+// Levels 1..NL of the N = 2^NL values v[] (one per plane of the group), each
+// written through st(level, plane within the group's share of it, value).
+template<typename T, int M, int NL, int J = 1, typename V, typename St>
+__device__ __forceinline__ void
+zrun_tree(const V (&v)[1 << (NL - J + 1)], St&& st)
+{
+    constexpr int N = 1 << (NL - J);
+    V o[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        if constexpr (std::is_same_v<V, T>) {
+            o[k] = reduce2<T, M>(v[2 * k], v[2 * k + 1]);
+        } else {
+#pragma unroll
+            for (int c = 0; c < int(sizeof(V) / sizeof(T)); ++c)
+                o[k].e[c] = reduce2<T, M>(v[2 * k].e[c], v[2 * k + 1].e[c]);
+        }
+        st(J, k, o[k]);
+    }
+    if constexpr (J < NL)
+        zrun_tree<T, M, NL, J + 1>(o, st);
+}
+
+template<typename T, int C>
+struct ZRunVec
+{
+    T e[C];
+};
+
+// EDGE: the span reaches past the plane's last whole vector — lanes past it
+// skip their loads and stores (exec mask); the reductions run on every lane,
+// so mean2's wave_any branch stays wave-uniform (§12.1's pattern).
+template<typename T, int M, int NL, bool EDGE>
+__device__ __forceinline__ void
+zrun_vectors(const ZRunParams& p, uint32_t g, uint64_t vec0, uint64_t nvec)
+{
+    constexpr int C = 16 / int(sizeof(T));
+    constexpr int P = 1 << NL;
+    constexpr int U = int(kZRunVecs);
+    using V = ZRunVec<T, C>;
+    const T* src = reinterpret_cast<const T*>(p.src) + uint64_t(g) * P * p.src_frame_elems;
+    V v[U][P] = {};
+    bool in[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+        in[u] = !EDGE || vec0 + uint64_t(u) * 64 < nvec;
+    // every load of the unit before the first reduction
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        if (in[u]) {
+#pragma unroll
+            for (int z = 0; z < P; ++z) {
+                if (M == kDecimate && z % 2 != 0)
+                    continue;
+                const T* a = src + uint64_t(z) * p.src_frame_elems + (vec0 + uint64_t(u) * 64) * C;
+                const u32x4 q = __builtin_nontemporal_load(reinterpret_cast<const u32x4_u*>(a));
+                __builtin_memcpy(&v[u][z], &q, 16);
+            }
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const uint64_t e0 = (vec0 + uint64_t(u) * 64) * C;
+        zrun_tree<T, M, NL>(v[u], [&](int j, int k, const V& o) {
+            if (in[u]) {
+                T* d = reinterpret_cast<T*>(p.dst[j - 1]) +
+                       (uint64_t(g) * (P >> j) + uint32_t(k)) * p.dst_frame_elems[j - 1] + e0;
+                store_vec<T, C, true>(d, o.e);
+            }
+        });
+    }
+}
+
+template<typename T, int M, int NL>
+__global__ __launch_bounds__(256) void
+zrun_kernel(ZRunParams p)
+{
+    constexpr int C = 16 / int(sizeof(T));
+    constexpr int P = 1 << NL;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t unit = blockIdx.x * (blockDim.x >> 6) + wave;
+    if (unit >= p.total_units)
+        return;
+    // spans fastest, then plane groups
+    const uint32_t g = unit / p.spans;
+    const uint32_t s = unit - g * p.spans;
+    const uint64_t nvec = p.elems / C;
+    const uint64_t span0 = uint64_t(s) * (64u * kZRunVecs);
+    if (span0 + 64u * kZRunVecs <= nvec)
+        zrun_vectors<T, M, NL, false>(p, g, span0 + lane, nvec);
+    else if (span0 < nvec)
+        zrun_vectors<T, M, NL, true>(p, g, span0 + lane, nvec);
+    if (C > 1 && s + 1 == p.spans) {
+        // the 1..C-1 elements behind the last whole vector, one to a lane
+        const uint32_t tail = uint32_t(p.elems - nvec * C);
+        if (tail == 0)
+            return;
+        const bool in = lane < tail;
+        const uint64_t e0 = nvec * C + lane;
+        const T* src = reinterpret_cast<const T*>(p.src) + uint64_t(g) * P * p.src_frame_elems;
+        T v[P] = {};
+        if (in) {
+#pragma unroll
+            for (int z = 0; z < P; ++z) {
+                if (M == kDecimate && z % 2 != 0)
+                    continue;
+                v[z] = src[uint64_t(z) * p.src_frame_elems + e0];
+            }
+        }
+        zrun_tree<T, M, NL>(v, [&](int j, int k, T o) {
+            if (in)
+                reinterpret_cast<T*>(p.dst[j - 1])[(uint64_t(g) * (P >> j) + uint32_t(k)) *
+                                                     p.dst_frame_elems[j - 1] +
+                                                   e0] = o;
+        });
+    }
+}
+
 // ---- chunk tiling --------------------------------------
 //
 // Array::write_frame_to_chunks_ (array.cpp:507-622) copies each frame tile's
@@ -2946,6 +3090,51 @@ AQZ_SHARDED(launch_zpair)(int dtype,
                                    static_cast<const T*>(earlier),
                                    static_cast<const T*>(current), n);
             return hipGetLastError();
+        });
+    });
+}
+
+hipError_t
+AQZ_SHARDED(launch_zrun)(int dtype,
+            int method,
+            const void* src,
+            uint64_t src_frame_elems,
+            uint64_t elems,
+            const LevelOut* outs,
+            int n_out,
+            uint32_t planes,
+            hipStream_t stream)
+{
+    const ZRunPlan pl = plan_zrun(dtype, method, src, src_frame_elems, elems, outs, n_out, planes);
+    if (!pl.valid)
+        return hipErrorInvalidValue;
+    ZRunParams p{};
+    p.src = static_cast<const uint8_t*>(src);
+    p.src_frame_elems = src_frame_elems;
+    p.elems = elems;
+    p.spans = pl.spans;
+    p.total_units = pl.groups * pl.spans;
+    for (int i = 0; i < n_out; ++i) {
+        p.dst[i] = static_cast<uint8_t*>(outs[i].ptr);
+        p.dst_frame_elems[i] = outs[i].frame_elems;
+    }
+    const dim3 grid(pl.grid), block(pl.block);
+    return with_dtype(dtype, [&](auto tag) -> hipError_t {
+        using T = decltype(tag);
+        return with_method(method, [&](auto mtag) -> hipError_t {
+            constexpr int M = decltype(mtag)::value;
+            if (launch_log_on())
+                launch_log_record("%s", format_plan(pl).c_str());
+            auto go = [&](auto nltag) -> hipError_t {
+                hipLaunchKernelGGL((zrun_kernel<T, M, decltype(nltag)::value>), grid, block, 0,
+                                   stream, p);
+                return hipGetLastError();
+            };
+            if (n_out == 1)
+                return go(int_tag<1>{});
+            if (n_out == 2)
+                return go(int_tag<2>{});
+            return go(int_tag<3>{});
         });
     });
 }

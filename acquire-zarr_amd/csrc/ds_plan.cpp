@@ -864,6 +864,102 @@ format_plan(const VolumeTiledPlan& p)
     return s.substr(0, 319); // the launch log's line length
 }
 
+ZRunPlan
+plan_zrun(int dtype, int method, const void* src, uint64_t src_frame_elems, uint64_t elems,
+          const LevelOut* outs, int n_out, uint32_t planes)
+{
+    ZRunPlan p;
+    const size_t b = dtype_bytes(dtype);
+    if (!b || !method_valid(method) || n_out < 1 || n_out > kMaxZLevels || planes == 0 ||
+        planes % (1u << n_out) != 0 || elems == 0 || elems > (~0ull >> 4) || !src || !outs ||
+        src_frame_elems < elems || reinterpret_cast<uintptr_t>(src) % b != 0)
+        return p;
+    for (int i = 0; i < n_out; ++i)
+        if (!outs[i].ptr || outs[i].frame_elems < elems ||
+            reinterpret_cast<uintptr_t>(outs[i].ptr) % b != 0)
+            return p;
+    p.dtype = dtype;
+    p.method = method;
+    p.n_out = n_out;
+    p.bytes = uint32_t(b);
+    p.planes = planes;
+    p.elems = elems;
+    p.groups = planes >> n_out;
+    // a plane's bytes in spans; the last one may hold no whole vector at all
+    // (the 1..15 bytes behind the last vector go from it element by element)
+    const uint64_t spans = (elems * b + kZRunSpanBytes - 1) / kZRunSpanBytes;
+    if (spans >= (1ull << 31) || spans * p.groups >= (1ull << 31))
+        return p;
+    p.spans = uint32_t(spans);
+    p.grid = grid_for(spans * p.groups, 4, 0);
+    p.valid = true;
+    return p;
+}
+
+std::string
+format_plan(const ZRunPlan& p)
+{
+    return line("family=zrun dtype=%u method=%d n_out=%d planes=%u groups=%u spans=%u "
+                "elems=%llu grid=%u block=%u",
+                p.bytes, p.method, p.n_out, p.planes, p.groups, p.spans,
+                static_cast<unsigned long long>(p.elems), p.grid, p.block);
+}
+
+int
+level_class(const PyramidLevel& in, const PyramidLevel& out)
+{
+    const bool xy = out.w < in.w || out.h < in.h;
+    const bool zh = out.planes < in.planes;
+    return xy ? (zh ? kClassXYZ : kClassXY) : (zh ? kClassZ : kClassNone);
+}
+
+PyramidRuns
+plan_pyramid_runs(const PyramidLevel* lv, uint32_t n_levels, uint32_t n_frames)
+{
+    PyramidRuns r;
+    const auto refuse = [&](const std::string& why) {
+        r.reason = why;
+        r.runs.clear();
+        return r;
+    };
+    if (!lv || n_levels < 2)
+        return refuse("fewer than two levels");
+    std::vector<int> cls(n_levels, kClassNone);
+    uint32_t zcount = 0;
+    for (uint32_t l = 1; l < n_levels; ++l) {
+        cls[l] = level_class(lv[l - 1], lv[l]);
+        if (cls[l] == kClassNone)
+            return refuse("level " + std::to_string(l) + " halves neither XY nor Z");
+        if (cls[l] == kClassXY)
+            continue;
+        if (lv[l - 1].planes % 2 != 0)
+            return refuse("level " + std::to_string(l) + " pairs an odd plane count");
+        if (lv[l].holds_plane)
+            return refuse("level " + std::to_string(l) + " holds an earlier plane");
+        if (++zcount >= 32)
+            return refuse("32 or more Z-halving levels");
+    }
+    if (n_frames == 0 || n_frames % (1u << zcount) != 0)
+        return refuse("frame count is no nonzero multiple of " + std::to_string(1u << zcount));
+    uint32_t frames = n_frames;
+    for (uint32_t l = 1; l < n_levels;) {
+        uint32_t end = l + 1;
+        while (end < n_levels && cls[end] == cls[l])
+            ++end;
+        const uint32_t depth = uint32_t(cls[l] == kClassXYZ  ? kMaxVolumeLevels
+                                        : cls[l] == kClassXY ? kMaxFusedLevels
+                                                             : kMaxZLevels);
+        for (; l < end; l += std::min(depth, end - l)) {
+            const uint32_t k = std::min(depth, end - l);
+            r.runs.push_back({ cls[l], l, k, frames });
+            if (cls[l] != kClassXY)
+                frames >>= k;
+        }
+    }
+    r.ok = true;
+    return r;
+}
+
 uint32_t
 tile_slices(uint32_t tile_rows, uint32_t tile_cols)
 {

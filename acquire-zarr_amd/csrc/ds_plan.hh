@@ -1,5 +1,6 @@
-// ds_plan.hh — what launch_cascade, launch_cascade_tiled, launch_volume and
-// launch_volume_tiled launch: host-only integer arithmetic over the dtype size, method, geometry,
+// ds_plan.hh — what launch_cascade, launch_cascade_tiled, launch_volume,
+// launch_volume_tiled and launch_zrun launch, and how a mixed pyramid is cut
+// into runs of them (plan_pyramid_runs): host-only integer arithmetic over the dtype size, method, geometry,
 // buffer alignment and the $AQZ_* A/B switches.  No HIP type appears here
 // (ds_plan.cpp builds with a plain C++ compiler; tests/cpp/plan_probe.cpp
 // runs it on the CPU).  ds_dispatch.cpp builds a plan per launch, logs
@@ -13,11 +14,17 @@
 #include <cstdlib>
 #include <functional>
 #include <string>
+#include <vector>
 
 namespace aqz {
 
 constexpr int kMaxFusedLevels = 4;
 constexpr int kMaxVolumeLevels = 2;
+constexpr int kMaxZLevels = 3;
+// zrun_kernel's unit: 64 lanes x kZRunVecs 16-byte vectors of every plane of
+// one plane group.
+constexpr uint32_t kZRunVecs = 2;
+constexpr uint32_t kZRunSpanBytes = 64 * kZRunVecs * 16;
 
 enum
 {
@@ -269,6 +276,23 @@ struct VolumeTiledPlan
     TiledLevelPlan lv[kMaxVolumeLevels];
 };
 
+// launch_zrun: `planes` consecutive frames of `elems` elements paired down
+// n_out times in Z alone.  One unit (a wave) is one plane group — 2^n_out
+// input planes — by one span of kZRunSpanBytes of the plane; `spans` is the
+// plane's bytes over that, rounded up, so the span that ends the plane also
+// carries the bytes behind its last whole 16-byte vector.  Units go spans
+// fastest, then groups, four to a workgroup.
+struct ZRunPlan
+{
+    bool valid = false;
+    int dtype = 0, method = 0, n_out = 0;
+    uint32_t bytes = 0;
+    // selectors: zrun_kernel<T, M, n_out>
+    uint32_t planes = 0, groups = 0, spans = 0;
+    uint64_t elems = 0;
+    uint32_t grid = 0, block = 256;
+};
+
 // `lds_cap`: the device's LDS per workgroup, less the band kernel's static
 // arrival counter (ds_dispatch.cpp asks the device once).
 CascadePlan plan_cascade(int dtype, int method, const void* src, uint64_t src_frame_elems,
@@ -290,11 +314,63 @@ VolumeTiledPlan plan_volume_tiled(int dtype, int method, const void* src,
                                   const LevelOut* outs, const TiledOut* touts, int n_out,
                                   uint32_t n_planes, const LaunchSwitches& sw);
 
+// Only outs[i].ptr and outs[i].frame_elems are read (a Z level keeps w x h).
+// Invalid: n_out outside 1..kMaxZLevels, `planes` zero or no multiple of
+// 2^n_out, elems zero, a frame stride (source or level) below elems, a null
+// or not element-aligned pointer, groups * spans at 2^31 or more.
+ZRunPlan plan_zrun(int dtype, int method, const void* src, uint64_t src_frame_elems,
+                   uint64_t elems, const LevelOut* outs, int n_out, uint32_t planes);
+
 // The launch log's line (launch_log.hh) for a valid plan: family=cascade or
-// family=band, family=tiled, family=volume, family=volume_tiled.
+// family=band, family=tiled, family=volume, family=volume_tiled, family=zrun.
 std::string format_plan(const CascadePlan& p);
 std::string format_plan(const TiledPlan& p);
 std::string format_plan(const VolumePlan& p);
 std::string format_plan(const VolumeTiledPlan& p);
+std::string format_plan(const ZRunPlan& p);
+
+// ---- pyramids as runs ---------------------------------------------------------
+// What a level (l >= 1) does to the one before it: halve XY and Z, XY alone,
+// Z alone, or neither (kClassNone: no batched launch takes it) — the
+// streaming handle's rule: XY when w or h shrinks, Z when the plane count
+// does.  Whether a run's exact extents fit its kernel is the launch plans'.
+enum
+{
+    kClassNone = 0,
+    kClassXYZ = 1,
+    kClassXY = 2,
+    kClassZ = 3
+};
+
+struct PyramidLevel
+{
+    uint32_t w = 0, h = 0, planes = 0;
+    bool holds_plane = false; // the level has stored the earlier plane of a pair
+};
+
+struct PyramidRun
+{
+    int cls = kClassNone;
+    uint32_t first = 0;     // the run's first level (>= 1)
+    uint32_t levels = 0;    // how many: <= kMaxVolumeLevels / kMaxFusedLevels / kMaxZLevels
+    uint32_t frames_in = 0; // frames of level first - 1 the run reads
+};
+
+struct PyramidRuns
+{
+    bool ok = false;
+    std::string reason; // why not, when !ok
+    std::vector<PyramidRun> runs;
+};
+
+int level_class(const PyramidLevel& in, const PyramidLevel& out);
+
+// Cuts levels 1..n_levels-1 into maximal stretches of one class, each in
+// pieces of that class's launch depth.  Level l emits n_frames >> zcount(l)
+// frames, zcount(l) the Z-halving levels among 1..l.  Refused: fewer than two
+// levels, 32 or more Z-halving ones, a level without a class, an odd plane count in
+// front of a Z-halving level, a Z-halving level that holds a plane, n_frames
+// zero or no multiple of 2^zcount(last).
+PyramidRuns plan_pyramid_runs(const PyramidLevel* lv, uint32_t n_levels, uint32_t n_frames);
 
 } // namespace aqz

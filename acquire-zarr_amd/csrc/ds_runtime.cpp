@@ -190,6 +190,9 @@ struct aqz_ds
     aqz::PinnedBuf h_stage;
     size_t device_bytes = 0;
     int last_batch_kind = -1;
+    // aqz_debug_ds_force_per_frame_batch: aqz_ds_run_device_batch takes the
+    // per-frame state machine (kind 0) whatever the pyramid
+    bool force_per_frame = false;
 
     // Small pyramids (all levels together <= kEagerBytes): every newly cached
     // level frame is copied to pinned host memory (Level::h_level) right
@@ -1715,10 +1718,100 @@ aqz_ds_run_device_batch(aqz_ds* ds,
             }
             return true;
         };
-        const bool batched_2d = pure_xy && n_frames > 0;
-        const bool volume = !batched_2d && pure_xyz && volume_takes_every_run();
+        const bool batched_2d = !ds->force_per_frame && pure_xy && n_frames > 0;
+        const bool volume =
+          !ds->force_per_frame && !batched_2d && pure_xyz && volume_takes_every_run();
 
-        if (batched_2d || volume) {
+        // Mixed pyramids (kind 7), only where both routes above pass: XYZ
+        // levels followed by an XY-only or a Z-only tail, or any other order
+        // of the three classes, cut into runs (plan_pyramid_runs) that chain
+        // through the caller's level buffers — launch_volume, launch_xy_run,
+        // launch_zrun — on the caller's stream.  Every run is planned before
+        // the first is queued; one the launchers would refuse leaves the
+        // whole call to the per-frame state machine, as a volume batch does.
+        aqz::PyramidRuns mixed;
+        const auto run_src = [&](const aqz::PyramidRun& r) -> const void* {
+            return r.first == 1 ? device_frames : device_out_levels[r.first - 1];
+        };
+        const auto mixed_takes_every_run = [&] {
+            std::vector<aqz::PyramidLevel> pl(ds->n);
+            for (uint32_t l = 0; l < ds->n; ++l) {
+                const Level& lv = ds->lv[l];
+                pl[l] = { lv.desc.width, lv.desc.height, lv.desc.planes, l > 0 && lv.has_partial };
+            }
+            mixed = aqz::plan_pyramid_runs(pl.data(), ds->n, n_frames);
+            if (!mixed.ok)
+                return false;
+            for (const aqz::PyramidRun& r : mixed.runs) {
+                aqz::LevelOut o[aqz::kMaxFusedLevels];
+                fill_outs(ds, r.first, r.levels, out_of, o);
+                const Level& a = ds->lv[r.first - 1];
+                const void* src = run_src(r);
+                bool ok = true;
+                if (r.cls == aqz::kClassXYZ) {
+                    ok = aqz::plan_volume(ds->dtype, ds->method, src, a.elems(), a.desc.width,
+                                          a.desc.height, o, int(r.levels), r.frames_in,
+                                          aqz::launch_switches())
+                           .valid;
+                } else if (r.cls == aqz::kClassXY) {
+                    // the fused cascade, or launch_xy_generic's rule level by level
+                    if (!aqz::cascade_supported(ds->dtype, src, a.elems(), a.desc.width,
+                                                a.desc.height, o, int(r.levels)))
+                        for (uint32_t j = 0; j < r.levels; ++j) {
+                            const aqz_level_desc& in = ds->lv[r.first + j - 1].desc;
+                            ok = ok && in.width && in.height && o[j].w == (in.width + 1) / 2 &&
+                                 o[j].h == (in.height + 1) / 2;
+                        }
+                } else {
+                    for (uint32_t j = 0; j < r.levels; ++j)
+                        ok = ok && o[j].w == a.desc.width && o[j].h == a.desc.height;
+                    ok = ok && aqz::plan_zrun(ds->dtype, ds->method, src, a.elems(), a.elems(), o,
+                                              int(r.levels), r.frames_in)
+                                 .valid;
+                }
+                if (!ok)
+                    return false;
+            }
+            return true;
+        };
+        const bool mixed_runs =
+          !ds->force_per_frame && !batched_2d && !volume && mixed_takes_every_run();
+
+        if (mixed_runs) {
+            for (const aqz::PyramidRun& r : mixed.runs) {
+                aqz::LevelOut o[aqz::kMaxFusedLevels];
+                fill_outs(ds, r.first, r.levels, out_of, o);
+                const Level& a = ds->lv[r.first - 1];
+                const void* src = run_src(r);
+                hipError_t e;
+                bool fused;
+                if (r.cls == aqz::kClassXYZ)
+                    e = aqz::launch_volume(ds->dtype, ds->method, src, a.elems(), a.desc.width,
+                                           a.desc.height, o, int(r.levels), r.frames_in,
+                                           ds->stream);
+                else if (r.cls == aqz::kClassXY)
+                    e = launch_xy_run(ds, src, r.first, r.levels, o, r.frames_in, ds->stream,
+                                      &fused);
+                else
+                    e = aqz::launch_zrun(ds->dtype, ds->method, src, a.elems(), a.elems(), o,
+                                         int(r.levels), r.frames_in, ds->stream);
+                if (e != hipSuccess) {
+                    rc = ds->fail(e, "batch mixed runs");
+                    break;
+                }
+            }
+            // as below: a failed launch leaves the counts where they were
+            if (rc == AQZ_OK) {
+                uint32_t frames = n_frames;
+                for (uint32_t l = 0; l < ds->n; ++l) {
+                    if (l > 0 && ds->lv[l].zh)
+                        frames >>= 1;
+                    emitted[l] = frames;
+                    ds->lv[l].count += frames;
+                }
+            }
+            ds->last_batch_kind = 7;
+        } else if (batched_2d || volume) {
             // Whole batch in batched launches; every frame / plane group independent.
             const uint32_t maxk = volume ? aqz::kMaxVolumeLevels : aqz::kMaxFusedLevels;
             const void* src = device_frames;
@@ -2552,6 +2645,15 @@ int
 aqz_ds_last_batch_kind(const aqz_ds* ds)
 {
     return ds ? ds->last_batch_kind : -1;
+}
+
+int
+aqz_debug_ds_force_per_frame_batch(aqz_ds* ds, int on)
+{
+    if (!ds)
+        return AQZ_INVALID_ARGUMENT;
+    ds->force_per_frame = on != 0;
+    return AQZ_OK;
 }
 
 uint64_t

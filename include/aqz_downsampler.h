@@ -403,7 +403,22 @@ int aqz_tile_frame_device_sliced(int dtype,
  * `device_out_levels[0]` is ignored.  `out_counts` (optional, n_levels
  * entries) receives the number of frames emitted per level.
  * Runs on `hip_stream` (NULL = the handle's own stream) and does not
- * synchronise; pure-2-D pyramids are one fused launch per 4 levels.
+ * synchronise; pure-2-D pyramids are one fused launch per 4 levels, pyramids
+ * whose levels all halve XY and Z one fused volume launch per 2 levels.
+ * Mixed pyramids — levels that halve XY and Z, XY alone or Z alone, in any
+ * order, as the level planner makes them for 3-D acquisitions (XYZ levels,
+ * then an XY-only or a Z-only tail) — run as a chain of batched launches
+ * through `device_out_levels` (aqz_ds_last_batch_kind 7): stretches of one
+ * class, cut into the fused volume kernel (2 levels), the fused cascade (4)
+ * and the Z-run kernel (3 levels that halve Z alone, from registers), all on
+ * `hip_stream`, with no wait on the handle's own stream and none on the host.
+ * Conditions: every level halves XY, Z or both; every level that halves Z has
+ * an even plane count in front of it and holds no earlier plane from a
+ * previous add_frame; `n_frames` is a nonzero multiple of 2^(levels that
+ * halve Z); every run fits its kernel.  Level L then emits
+ * n_frames >> (levels 1..L that halve Z) frames.  Any other pyramid or batch
+ * takes the per-frame state machine (kind 0), which queues one launch per
+ * plane per level and joins the handle's stream; the bytes are the same.
  */
 int aqz_ds_run_device_batch(aqz_ds* ds,
                             const void* device_frames,
@@ -674,9 +689,20 @@ int aqz_ds_run_host_batch(aqz_ds* ds,
  * 5 = fused volume writing chunk tiles (aqz_ds_run_device_volume_tiled),
  * 6 = fused 2-D cascade writing chunk tiles, base included
  * (aqz_ds_run_device_batch_tiled_base / _chunked_base),
+ * 7 = mixed pyramid as a chain of batched runs (fused volume, fused cascade
+ * or batched single-level XY kernels, Z run; aqz_ds_run_device_batch),
  * -1 = none.
  */
 int aqz_ds_last_batch_kind(const aqz_ds* ds);
+
+/*
+ * Test seam: while `on` is nonzero, aqz_ds_run_device_batch on this handle
+ * takes none of its batched routes (kinds 1, 2, 3 and 7) and runs the
+ * per-frame state machine (kind 0) — the A/B partner of the batched routes
+ * and the reference of their "same bytes" tests.  AQZ_OK, or
+ * AQZ_INVALID_ARGUMENT for a null handle.
+ */
+int aqz_debug_ds_force_per_frame_batch(aqz_ds* ds, int on);
 
 /*
  * Diagnostic: how many runs of pure-XY levels the streaming path (add_frame)
@@ -725,10 +751,10 @@ const char* aqz_version(void);
  * Test seam: the launch log.  With $AQZ_LAUNCH_LOG=1 in the environment when
  * the library launches its first kernel, every kernel launcher (the fused
  * cascade and its band form, the chunk-tiled cascade, the fused volume, the
- * generic XY and Z-pair kernels, the blosc filters) records the kernel it
+ * generic XY, Z-pair and Z-run kernels, the blosc filters) records the kernel it
  * chose, one line of space-separated key=value pairs per launch, in a
  * process-wide ring of the last 512 launches; unset, nothing is recorded.
- * Every line has `family` (cascade, band, tiled, volume, generic, zpair,
+ * Every line has `family` (cascade, band, tiled, volume, generic, zpair, zrun,
  * shuffle, bitshuffle, copy), `dtype` (bytes per element), `method`, `n_out`,
  * `grid` and `block`, and the fields of its launcher's A/B switches
  * (acquire-zarr_amd/csrc/launch_log.hh, tests/test_gpu_launch_rules.py).
