@@ -1,8 +1,13 @@
 // blosc_decode_sweep — csrc/blosc_decode.hh under the host sanitizers: the
 // serial LZ4 block decoder, the frame walker and the unfilter over valid
-// blocks and frames, then over seeded single-byte flips and truncations of
-// them.  Every buffer is allocated exactly to size, so an access one byte
-// outside a block, a frame, a chunk or the scratch is an ASan report.
+// blocks and frames, then over seeded mutations of them: bit flips, bytes set
+// to 0x00 / 0xFF / 0x0F / 0xF0, truncations, appended bytes, every prefix of
+// two blocks of about 600 bytes, and blocks whose offset pair, literal run and
+// match run straddle input bytes 255|256 (where the device decoder refills its
+// window) — the kinds tests/decode_mutation_cases.py gives the device decoder
+// with this code's answers as the expectation.  Every buffer is allocated
+// exactly to size, so an access one byte outside a block, a frame, a chunk or
+// the scratch is an ASan report.
 //
 //   make -C acquire-zarr_amd bloscdecodesweep && tests/cpp/bin/blosc_decode_sweep
 //
@@ -17,6 +22,7 @@
 #include <cstring>
 #include <memory>
 #include <random>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -157,6 +163,100 @@ struct Frame
     uint32_t ts;
 };
 
+// One sequence of a block written from the format, and where the writer put
+// its offset pair and its length-run bytes.
+struct Seq
+{
+    size_t lit;
+    uint32_t off, ml;
+};
+
+struct Written
+{
+    Bytes block;
+    size_t plain = 0;
+    std::vector<size_t> offset_at;
+    std::vector<std::vector<size_t>> lit_run, ml_run;
+};
+
+void
+put_run(Bytes& b, size_t n, std::vector<size_t>* at)
+{
+    for (n -= 15;; n -= 255) {
+        if (at)
+            at->push_back(b.size());
+        b.push_back(uint8_t(n < 255 ? n : 255));
+        if (n < 255)
+            break;
+    }
+}
+
+Written
+write_block(std::mt19937& rng, const std::vector<Seq>& seqs, size_t last)
+{
+    Written w;
+    for (const Seq& s : seqs) {
+        const size_t m = s.ml - 4;
+        w.block.push_back(uint8_t(((s.lit < 15 ? s.lit : 15) << 4) | (m < 15 ? m : 15)));
+        w.lit_run.emplace_back();
+        w.ml_run.emplace_back();
+        if (s.lit >= 15)
+            put_run(w.block, s.lit, &w.lit_run.back());
+        for (size_t i = 0; i < s.lit; ++i)
+            w.block.push_back(uint8_t(rng()));
+        w.offset_at.push_back(w.block.size());
+        w.block.push_back(uint8_t(s.off));
+        w.block.push_back(uint8_t(s.off >> 8));
+        if (m >= 15)
+            put_run(w.block, m, &w.ml_run.back());
+        w.plain += s.lit + s.ml;
+    }
+    w.block.push_back(uint8_t((last < 15 ? last : 15) << 4));
+    if (last >= 15)
+        put_run(w.block, last, nullptr);
+    for (size_t i = 0; i < last; ++i)
+        w.block.push_back(uint8_t(rng()));
+    w.plain += last;
+    return w;
+}
+
+bool
+holds(const std::vector<size_t>& v, size_t a, size_t b)
+{
+    bool fa = false, fb = false;
+    for (size_t x : v) {
+        fa |= x == a;
+        fb |= x == b;
+    }
+    return fa && fb;
+}
+
+// decode a block with both buffers exact; the result is a size within cap or
+// a named error
+int32_t
+decode_block_exact(const Bytes& b, size_t cap)
+{
+    Exact src(b.data(), b.size()), dst(cap);
+    const int32_t r =
+      aqz::lz4::decode_block(src.get(), uint32_t(b.size()), dst.get(), uint32_t(cap));
+    CHECK(r >= aqz::lz4::kDecEndsInMatch && r <= int32_t(cap), "mutated block of %zu bytes: %d",
+          b.size(), r);
+    return r;
+}
+
+size_t
+draw_cap(std::mt19937& rng, size_t n)
+{
+    switch (rng() % 4) {
+        case 0: return n;
+        case 1: return n ? n - 1 : 0;
+        case 2: return n + 9;
+        default: return rng() % (n + 1);
+    }
+}
+
+const uint8_t kSetValues[4] = { 0x00, 0xFF, 0x0F, 0xF0 };
+
 // decode with every buffer exact; returns the status, fills *out on kOk
 Status
 decode_exact(const uint8_t* frame, size_t extent, uint32_t ts, uint32_t nbytes, Bytes* out)
@@ -197,18 +297,89 @@ main()
         }
         for (int m = 0; m < 40; ++m) {
             Bytes mut = b;
-            if (rng() % 4 == 0)
+            const unsigned what = rng() % 8;
+            if (what < 2)
                 mut.resize(rng() % mut.size());
-            else
+            else if (what < 5)
                 mut[rng() % mut.size()] ^= uint8_t(1u << (rng() % 8));
-            const size_t cap = (rng() % 3) ? n : rng() % (n + 1);
-            Exact src(mut.data(), mut.size()), dst(cap);
-            const int32_t r = aqz::lz4::decode_block(src.get(), uint32_t(mut.size()), dst.get(),
-                                                     uint32_t(cap));
-            CHECK(r >= aqz::lz4::kDecEndsInMatch && r <= int32_t(cap), "mutated block %zu: %d", k, r);
+            else if (what < 7)
+                mut[rng() % mut.size()] = kSetValues[rng() % 4];
+            else
+                for (unsigned extra = 1 + rng() % 3; extra; --extra)
+                    mut.push_back(uint8_t(rng()));
+            const int32_t r = decode_block_exact(mut, draw_cap(rng, n));
             ++n_mut;
             n_refused += r < 0;
         }
+    }
+    // every prefix of two blocks of about 600 bytes: an encoder's, and one of
+    // many short sequences written from the format
+    {
+        std::vector<Seq> seqs;
+        size_t plain = 0;
+        for (int i = 0; i < 26; ++i) {
+            Seq q;
+            q.lit = (plain ? 0 : 1) + rng() % 40 + (rng() % 8 ? 0 : 15);
+            plain += q.lit;
+            q.off = uint32_t(1 + rng() % plain);
+            q.ml = rng() % 6 ? uint32_t(4 + rng() % 37) : uint32_t(19 + rng() % 300);
+            plain += q.ml;
+            seqs.push_back(q);
+        }
+        const Written w = write_block(rng, seqs, 12);
+        const Bytes echo = make_data(rng, 4, 1100);
+        const Bytes enc = encode(echo, 1);
+        CHECK(decode_block_exact(w.block, w.plain) == int32_t(w.plain), "written block");
+        CHECK(w.block.size() > 400 && w.block.size() < 900 && enc.size() > 400 && enc.size() < 900,
+              "prefix blocks of %zu and %zu bytes", w.block.size(), enc.size());
+        for (const auto& [blk, n] : { std::pair<const Bytes&, size_t>{ w.block, w.plain },
+                                      std::pair<const Bytes&, size_t>{ enc, echo.size() } })
+            for (size_t cut = 0; cut < blk.size(); ++cut) {
+                const int32_t r =
+                  decode_block_exact(Bytes(blk.begin(), blk.begin() + cut), draw_cap(rng, n));
+                ++n_mut;
+                n_refused += r < 0;
+            }
+    }
+    // an offset pair, a literal run and a match run across input bytes 255|256
+    {
+        size_t n_straddle = 0;
+        for (int kind = 0; kind < 3; ++kind)
+            for (size_t L = 0; L < 300; ++L) {
+                std::vector<Seq> seqs = { { 40, 40, 300 } };
+                if (kind == 0) {
+                    seqs.push_back({ L, 0x0123, 20 });
+                } else if (kind == 1) {
+                    seqs.push_back({ L, 7, 8 });
+                    seqs.push_back({ 15 + 510 + 9, 300, 8 });
+                } else {
+                    seqs.push_back({ L, 7, 19 + 510 + 9 });
+                }
+                const Written w = write_block(rng, seqs, 12);
+                const bool hit = kind == 0   ? w.offset_at[1] == 255
+                                 : kind == 1 ? holds(w.lit_run[2], 255, 256)
+                                             : holds(w.ml_run[1], 255, 256);
+                if (!hit)
+                    continue;
+                ++n_straddle;
+                CHECK(decode_block_exact(w.block, w.plain) == int32_t(w.plain), "straddle %d", kind);
+                CHECK(decode_block_exact(w.block, w.plain + 9) == int32_t(w.plain), "straddle %d",
+                      kind);
+                for (size_t at : { size_t(255), size_t(256) })
+                    for (unsigned bit = 0; bit < 8; ++bit) {
+                        Bytes mut = w.block;
+                        mut[at] ^= uint8_t(1u << bit);
+                        n_refused += decode_block_exact(mut, draw_cap(rng, w.plain)) < 0;
+                        ++n_mut;
+                    }
+                for (size_t cut : { size_t(255), size_t(256), size_t(257) }) {
+                    n_refused += decode_block_exact(Bytes(w.block.begin(), w.block.begin() + cut),
+                                                    draw_cap(rng, w.plain)) < 0;
+                    ++n_mut;
+                }
+                break;
+            }
+        CHECK(n_straddle == 3, "straddling blocks found: %zu", n_straddle);
     }
     // ---- frames ------------------------------------------------------------
     std::vector<Frame> frames;
@@ -235,15 +406,23 @@ main()
         const Status st = decode_exact(fr.bytes.data(), fr.bytes.size(), fr.ts, n, &out);
         CHECK(st == aqz::blosc::kOk && out == fr.src, "frame %zu: status %u", k, unsigned(st));
         ++f_valid;
-        for (int m = 0; m < 12; ++m) {
+        for (int m = 0; m < 16; ++m) {
             Bytes mut = fr.bytes;
-            const unsigned what = rng() % 8;
+            const unsigned what = rng() % 12;
+            const size_t head = mut.size() < 48 ? mut.size() : 48;
             if (what == 0)
                 mut.resize(rng() % mut.size());
             else if (what < 4) // the header, block starts and first sizes steer the walk
-                mut[rng() % (mut.size() < 48 ? mut.size() : 48)] ^= uint8_t(1u << (rng() % 8));
-            else
+                mut[rng() % head] ^= uint8_t(1u << (rng() % 8));
+            else if (what < 7)
                 mut[rng() % mut.size()] ^= uint8_t(1u << (rng() % 8));
+            else if (what < 9)
+                mut[rng() % head] = kSetValues[rng() % 4];
+            else if (what < 11)
+                mut[rng() % mut.size()] = kSetValues[rng() % 4];
+            else
+                for (unsigned extra = 1 + rng() % 3; extra; --extra)
+                    mut.push_back(uint8_t(rng()));
             const Status ms = decode_exact(mut.data(), mut.size(), fr.ts, n, nullptr);
             CHECK(ms <= aqz::blosc::kCorrupt && ms != aqz::blosc::kAbsent, "mutated frame %zu", k);
             ++f_mut;
@@ -272,6 +451,6 @@ main()
     std::printf("blocks: %zu valid, %zu mutated (%zu refused); frames: %zu valid, %zu mutated "
                 "(%zu refused); %d failures\n",
                 n_valid, n_mut, n_refused, f_valid, f_mut, f_refused, failures);
-    CHECK(n_mut + f_mut >= 3000 && n_refused > 200 && f_refused > 200, "too few mutations bite");
+    CHECK(n_mut + f_mut >= 5500 && n_refused > 2000 && f_refused > 800, "too few mutations bite");
     return failures ? 1 : 0;
 }
