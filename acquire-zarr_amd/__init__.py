@@ -46,6 +46,8 @@ EXPORTS = (
     "aqz_ds_run_device_volume_tiled", "aqz_ds_run_device_volume_chunked",
     "aqz_ds_run_device_batch_tiled_base", "aqz_ds_run_device_batch_chunked_base",
     "aqz_ds_tiled_base_flag_slots",
+    "aqz_ds_run_device_mixed_tiled", "aqz_ds_run_device_mixed_chunked",
+    "aqz_ds_mixed_flag_slots",
     "aqz_blosc_blocksize", "aqz_blosc_frame_from_filtered", "aqz_blosc_ctx_create",
     "aqz_blosc_ctx_destroy", "aqz_blosc_compress_device", "aqz_blosc_codec_info",
     "aqz_blosc_lz4_frames_device", "aqz_blosc_lz4_compress_device",
@@ -210,6 +212,10 @@ def lib() -> ctypes.CDLL:
                                                   ctypes.POINTER(vp), ctypes.POINTER(u32), vp]
     L.aqz_ds_run_device_volume_tiled.argtypes = L.aqz_ds_run_device_batch_tiled.argtypes
     L.aqz_ds_run_device_volume_chunked.argtypes = L.aqz_ds_run_device_batch_chunked.argtypes
+    L.aqz_ds_run_device_mixed_tiled.argtypes = L.aqz_ds_run_device_batch_tiled.argtypes
+    L.aqz_ds_run_device_mixed_chunked.argtypes = L.aqz_ds_run_device_batch_chunked.argtypes
+    L.aqz_ds_mixed_flag_slots.argtypes = [vp, u32, u32, u32]
+    L.aqz_ds_mixed_flag_slots.restype = u32
     L.aqz_ds_run_device_batch_tiled_base.argtypes = L.aqz_ds_run_device_batch_tiled.argtypes
     L.aqz_ds_run_device_batch_chunked_base.argtypes = \
         L.aqz_ds_run_device_batch_chunked.argtypes
@@ -480,7 +486,8 @@ class Downsampler:
         some runs on batched single-level kernels, 4 fused 2-D cascade writing
         chunk tiles, 5 fused volume writing chunk tiles, 6 tiled cascade with
         its base, 7 mixed pyramid as a chain of batched runs (volume, cascade,
-        Z run), -1 none."""
+        Z run), 8 mixed pyramid as a chain of fused runs writing chunk tiles,
+        -1 none."""
         return lib().aqz_ds_last_batch_kind(self._h)
 
     def debug_force_per_frame_batch(self, on) -> None:
@@ -727,6 +734,54 @@ class Downsampler:
             self._h, device_frames, n_frames, arr, nz, counts,
             ctypes.c_void_p(stream) if stream else None))
         return list(counts)
+
+    def run_device_mixed_tiled(self, device_frames: int, n_frames: int, tiles,
+                               device_outs, device_nonzero=None, stream: int = 0):
+        """run_device_batch_tiled for a mixed 3-D pyramid (levels that halve
+        XYZ, XY alone or Z alone, in runs of one class): level L emits
+        n_frames >> zcount(L) frames, tiled as there, with
+        mixed_flag_slots(L, ...) flag bytes per tile per frame in
+        `device_nonzero[L]`.  Returns frames emitted per level."""
+        n = self.n_levels
+        tr = (ctypes.c_uint32 * n)(*[int(t[0]) if t else 0 for t in tiles])
+        tc = (ctypes.c_uint32 * n)(*[int(t[1]) if t else 0 for t in tiles])
+        outs = (ctypes.c_void_p * n)(*[int(p) if p else 0 for p in device_outs])
+        nz = None
+        if device_nonzero is not None:
+            nz = (ctypes.c_void_p * n)(*[int(p) if p else 0 for p in device_nonzero])
+        counts = (ctypes.c_uint32 * n)()
+        self._check(lib().aqz_ds_run_device_mixed_tiled(
+            self._h, device_frames, n_frames, tr, tc, outs, nz, counts,
+            ctypes.c_void_p(stream) if stream else None))
+        return list(counts)
+
+    def run_device_mixed_chunked(self, device_frames: int, n_frames: int, lattices,
+                                 device_nonzero=None, stream: int = 0):
+        """aqz_ds_run_device_mixed_chunked: `lattices[L]` as for
+        run_device_batch_chunked, its frame_offset_bytes list holding one
+        entry per frame level L emits (n_frames >> zcount(L))."""
+        n = self.n_levels
+        arr = (ChunkLattice * n)()
+        keep = []
+        for L in range(1, n):
+            base, cap, tr, tc, stride, offs = lattices[L]
+            offs = list(offs)
+            o = (ctypes.c_uint64 * max(len(offs), 1))(*offs)
+            keep.append(o)
+            arr[L] = ChunkLattice(int(base) if base else 0, cap, tr, tc, stride, o)
+        nz = None
+        if device_nonzero is not None:
+            nz = (ctypes.c_void_p * n)(*[int(p) if p else 0 for p in device_nonzero])
+        counts = (ctypes.c_uint32 * n)()
+        self._check(lib().aqz_ds_run_device_mixed_chunked(
+            self._h, device_frames, n_frames, arr, nz, counts,
+            ctypes.c_void_p(stream) if stream else None))
+        return list(counts)
+
+    def mixed_flag_slots(self, level: int, tile_rows: int, tile_cols: int) -> int:
+        """Zero-scan flag bytes per tile of run_device_mixed_tiled at `level`
+        (0: bad level or shape, or a pyramid the run planner cannot class)."""
+        return lib().aqz_ds_mixed_flag_slots(self._h, level, tile_rows, tile_cols)
 
     def batch_call(self, device_frames: int, n_frames: int, device_outs, stream: int = 0,
                    tiles=None, device_nonzero=None):

@@ -154,6 +154,11 @@ AQZ_FORWARD(launch_zrun,
             (int dtype, int method, const void* src, uint64_t src_frame_elems, uint64_t elems,
              const LevelOut* outs, int n_out, uint32_t planes, hipStream_t stream),
             (dtype, method, src, src_frame_elems, elems, outs, n_out, planes, stream))
+AQZ_FORWARD(launch_zrun_tiled,
+            (int dtype, int method, const void* src, uint64_t src_frame_elems, uint32_t W,
+             uint32_t H, const LevelOut* outs, const TiledOut* touts, int n_out, uint32_t planes,
+             hipStream_t stream),
+            (dtype, method, src, src_frame_elems, W, H, outs, touts, n_out, planes, stream))
 AQZ_FORWARD(launch_transpose,
             (int dtype, const void* src, uint32_t rows, uint32_t cols, void* dst,
              hipStream_t stream),

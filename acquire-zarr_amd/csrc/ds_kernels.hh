@@ -90,6 +90,19 @@ hipError_t launch_zrun(int dtype, int method, const void* src, uint64_t src_fram
                        uint64_t elems, const LevelOut* outs, int n_out, uint32_t planes,
                        hipStream_t stream);
 
+// launch_zrun over planes of W x H elements with every level written
+// chunk-tiled from registers, plane k of level j as frame k of touts[j-1]
+// (planes >> j planes: that many frame_offsets entries for a chunk lattice),
+// each level in its own tile shape.  One kernel; its first waves zero-fill
+// the tile overhang; touts[i].nonzero, when set, is cleared by a fill queued
+// first and holds one byte per tile per emitted plane.  outs[i].ptr, when
+// non-null, also receives the level row-major (the input of a following
+// launch).  Planned by plan_zrun_tiled (ds_plan.hh).
+hipError_t launch_zrun_tiled(int dtype, int method, const void* src, uint64_t src_frame_elems,
+                             uint32_t W, uint32_t H, const LevelOut* outs,
+                             const TiledOut* touts, int n_out, uint32_t planes,
+                             hipStream_t stream);
+
 // Chunk tiling of one W x H frame (array.cpp:507-622 / chunk.cpp:17-58):
 // transpose_frame (array.cpp:488-504): `dst` (cols x rows, row-major)
 // receives the transpose of `src` (rows x cols, row-major).

@@ -2244,6 +2244,259 @@ zrun_kernel(ZRunParams p)
     }
 }
 
+// ---- Z run, chunk-tiled ------------------------------------------------------
+//
+// zrun_kernel with every level also (dst[j] null: only) written in chunk-tile
+// order, plane k of level j + 1 as frame k of tl[j] (launch_zrun_tiled).  The
+// planes are W x H (elems = W * H); units, loads and the tree are
+// zrun_kernel's.  A lane turns its vector's first element e into
+// (y, x) = (e / W, e % W): the span's first element is divided once per wave
+// (uniform), the lane's offset behind it — below 2^12 — by FastDiv.  Per
+// level, with that level's own tile shape, a vector whose C elements lie in
+// one frame row and one tile row is one 16-byte store; any other goes element
+// by element, the address worked out anew only where a frame row or a tile
+// row ends.  The stores cover exactly the frame; the grid's first zwaves /
+// (waves per block) blocks zero-fill the rest of the padded area
+// (zero_fill_tiled<T, NL>, cov_w = W and cov_h = H).  One flag byte per tile,
+// cleared before the launch, set to 1 by every lane storing a nonzero bit
+// pattern into the tile.  tl[] has the cascade's length for zero_fill_tiled.
+struct ZRunTiledParams : ZRunParams
+{
+    uint32_t W;
+    FastDiv dw; // by W
+    TiledLevel tl[kMaxFusedLevels];
+    uint32_t zitems; // zero-fill items per plane group, all levels
+    FastDiv zdiv;    // by zitems
+    uint32_t zwaves;
+};
+
+// Row and column of plane element `base` (wave-uniform).
+__device__ __forceinline__ void
+zrun_row_col(const ZRunTiledParams& p, uint64_t base, uint32_t& y, uint32_t& x)
+{
+    if ((p.elems >> 32) == 0) {
+        y = p.dw.div(uint32_t(base));
+        x = uint32_t(base) - y * p.W;
+    } else {
+        const uint64_t q = base / p.W;
+        y = uint32_t(q);
+        x = uint32_t(base - q * p.W);
+    }
+}
+
+// N consecutive plane elements e[], the first at (y, x), into frame `plane`
+// of tiled level t.  Every element lies inside the plane.
+template<typename T, int N>
+__device__ __forceinline__ void
+zrun_store_tiled(const TiledLevel& t, uint32_t W, uint32_t plane, uint32_t y, uint32_t x,
+                 const T (&e)[N])
+{
+    T* base = reinterpret_cast<T*>(t.tdst) + tiled_frame_base(t, plane);
+    uint8_t* flags = t.flags ? t.flags + uint64_t(plane) * t.flags_frame : nullptr;
+    uint32_t ty = t.dr.div(y), tx = t.dc.div(x);
+    uint32_t ry = y - ty * t.tr, cx = x - tx * t.tc;
+    const auto at = [&]() {
+        return base + (uint64_t(ty) * t.ntx + tx) * t.tstride + uint64_t(ry) * t.tc + cx;
+    };
+    if (N == 1 || (x + N <= W && cx + N <= t.tc)) {
+        bool nz = false;
+#pragma unroll
+        for (int c = 0; c < N; ++c)
+            nz = nz || nonzero_bits(e[c]);
+        store_vec<T, N, true>(at(), e);
+        if (flags && nz)
+            flags[ty * t.ntx + tx] = 1;
+        return;
+    }
+    if constexpr (N > 1) {
+        // a rolled loop over the 16 bytes as one integer, the next element
+        // shifted down each turn: no register is indexed by the counter
+        static_assert(N * sizeof(T) == 16, "a lane's vector");
+        unsigned __int128 q;
+        __builtin_memcpy(&q, e, 16);
+        T* d = at();
+#pragma clang loop unroll(disable)
+        for (int c = 0; c < N; ++c) {
+            const uint64_t lo = uint64_t(q);
+            T one[1];
+            __builtin_memcpy(one, &lo, sizeof(T));
+            store_vec<T, 1, true>(d, one);
+            if (flags && nonzero_bits(one[0]))
+                flags[ty * t.ntx + tx] = 1;
+            q >>= 8 * sizeof(T);
+            ++x;
+            ++cx;
+            ++d;
+            if (x == W) {
+                // the frame row ends: the next row's first tile
+                x = 0;
+                ++y;
+                ty = t.dr.div(y);
+                ry = y - ty * t.tr;
+                tx = 0;
+                cx = 0;
+                d = at();
+            } else if (cx == t.tc) {
+                // the tile row ends: the same row of the next tile
+                ++tx;
+                cx = 0;
+                d = at();
+            }
+        }
+    }
+}
+
+// Level I + 1 of a unit's outputs (levels[j][k]: level j + 1, plane k of the
+// group's share), N elements a lane store, row-major where dst[I] is set and
+// as tiles.  One level after the other, each with its TiledLevel at a
+// compile-time place in the kernel arguments, so that one level's scalars are
+// live at a time.
+template<typename T, int NL, int N, int U, int I = 0, typename V>
+__device__ __forceinline__ void
+zrun_store_levels(const ZRunTiledParams& p, uint32_t g, const V (&levels)[U][NL][(1 << NL) / 2],
+                  const bool (&in)[U], const uint64_t (&e0)[U], const uint32_t (&y)[U],
+                  const uint32_t (&x)[U])
+{
+    if constexpr (I < NL) {
+        constexpr int PL = (1 << NL) >> (I + 1); // the level's planes per group
+        const TiledLevel t = p.tl[I];            // one kernarg block load
+        T* rm = reinterpret_cast<T*>(p.dst[I]);
+        const uint64_t rm_frame = p.dst_frame_elems[I];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (in[u]) {
+#pragma unroll
+                for (int k = 0; k < PL; ++k) {
+                    const uint32_t plane = g * uint32_t(PL) + uint32_t(k);
+                    T e[N];
+                    __builtin_memcpy(e, &levels[u][I][k], sizeof(e));
+                    if (rm)
+                        store_vec<T, N, true>(rm + uint64_t(plane) * rm_frame + e0[u], e);
+                    zrun_store_tiled<T, N>(t, p.W, plane, y[u], x[u], e);
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        zrun_store_levels<T, NL, N, U, I + 1>(p, g, levels, in, e0, y, x);
+    }
+}
+
+// zrun_vectors with the tiled stores.  (y0, x0): row and column of the span's
+// first element (uniform); x0 + the lane's offset stays below 2^31 + 2^12.
+template<typename T, int M, int NL, bool EDGE>
+__device__ __forceinline__ void
+zrun_tiled_vectors(const ZRunTiledParams& p, uint32_t g, uint64_t vec0, uint64_t nvec,
+                   uint32_t y0, uint32_t x0, uint32_t lane)
+{
+    constexpr int C = 16 / int(sizeof(T));
+    constexpr int P = 1 << NL;
+    constexpr int U = int(kZRunVecs);
+    using V = ZRunVec<T, C>;
+    const T* src = reinterpret_cast<const T*>(p.src) + uint64_t(g) * P * p.src_frame_elems;
+    V v[U][P] = {};
+    bool in[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+        in[u] = !EDGE || vec0 + uint64_t(u) * 64 < nvec;
+    // every load of the unit before the first reduction
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        if (in[u]) {
+#pragma unroll
+            for (int z = 0; z < P; ++z) {
+                if (M == kDecimate && z % 2 != 0)
+                    continue;
+                const T* a = src + uint64_t(z) * p.src_frame_elems + (vec0 + uint64_t(u) * 64) * C;
+                const u32x4 q = __builtin_nontemporal_load(reinterpret_cast<const u32x4_u*>(a));
+                __builtin_memcpy(&v[u][z], &q, 16);
+            }
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // the whole tree on every lane, then the stores, masked
+    V levels[U][NL][P / 2];
+    uint64_t e0[U];
+    uint32_t y[U], x[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        zrun_tree<T, M, NL>(v[u], [&](int j, int k, const V& o)
+                                    __attribute__((always_inline)) { levels[u][j - 1][k] = o; });
+        e0[u] = (vec0 + uint64_t(u) * 64) * C;
+        // the vector's first element as (y, x): one division by W
+        const uint32_t xx = x0 + (lane + uint32_t(u) * 64) * uint32_t(C);
+        const uint32_t dy = p.dw.div(xx);
+        y[u] = y0 + dy;
+        x[u] = xx - dy * p.W;
+    }
+    zrun_store_levels<T, NL, C, U>(p, g, levels, in, e0, y, x);
+}
+
+template<typename T, int M, int NL>
+__global__ __launch_bounds__(256) void
+zrun_tiled_kernel(ZRunTiledParams p)
+{
+    constexpr int C = 16 / int(sizeof(T));
+    constexpr int P = 1 << NL;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t wpb = blockDim.x >> 6;
+    uint32_t blk = blockIdx.x;
+    // The first blocks zero-fill the tile overhang, as in volume_kernel.
+    const uint32_t zb = p.zwaves / wpb;
+    if (blk < zb) {
+        zero_fill_tiled<T, NL>(p, blk * wpb + wave, p.zwaves, int(lane), NL,
+                               p.total_units / p.spans);
+        return;
+    }
+    blk -= zb;
+    const uint32_t unit = blk * wpb + wave;
+    if (unit >= p.total_units)
+        return;
+    // spans fastest, then plane groups
+    const uint32_t g = unit / p.spans;
+    const uint32_t s = unit - g * p.spans;
+    const uint64_t nvec = p.elems / C;
+    const uint64_t span0 = uint64_t(s) * (64u * kZRunVecs);
+    if (span0 < nvec) {
+        uint32_t y0, x0;
+        zrun_row_col(p, span0 * C, y0, x0);
+        if (span0 + 64u * kZRunVecs <= nvec)
+            zrun_tiled_vectors<T, M, NL, false>(p, g, span0 + lane, nvec, y0, x0, lane);
+        else
+            zrun_tiled_vectors<T, M, NL, true>(p, g, span0 + lane, nvec, y0, x0, lane);
+    }
+    if (C > 1 && s + 1 == p.spans) {
+        // the 1..C-1 elements behind the last whole vector, one to a lane
+        const uint32_t tail = uint32_t(p.elems - nvec * C);
+        if (tail == 0)
+            return;
+        const bool in = lane < tail;
+        const uint64_t e0 = nvec * C + lane;
+        uint32_t y0, x0;
+        zrun_row_col(p, nvec * C, y0, x0);
+        const uint32_t xx = x0 + lane;
+        const uint32_t dy = p.dw.div(xx);
+        const uint32_t y = y0 + dy, x = xx - dy * p.W;
+        const T* src = reinterpret_cast<const T*>(p.src) + uint64_t(g) * P * p.src_frame_elems;
+        T v[P] = {};
+        if (in) {
+#pragma unroll
+            for (int z = 0; z < P; ++z) {
+                if (M == kDecimate && z % 2 != 0)
+                    continue;
+                v[z] = src[uint64_t(z) * p.src_frame_elems + e0];
+            }
+        }
+        T levels[1][NL][P / 2];
+        zrun_tree<T, M, NL>(v, [&](int j, int k, T o)
+                                 __attribute__((always_inline)) { levels[0][j - 1][k] = o; });
+        const bool in1[1] = { in };
+        const uint64_t e1[1] = { e0 };
+        const uint32_t y1[1] = { y }, x1[1] = { x };
+        zrun_store_levels<T, NL, 1, 1>(p, g, levels, in1, e1, y1, x1);
+    }
+}
+
 // ---- chunk tiling --------------------------------------
 //
 // Array::write_frame_to_chunks_ (array.cpp:507-622) copies each frame tile's
@@ -3128,6 +3381,67 @@ AQZ_SHARDED(launch_zrun)(int dtype,
             auto go = [&](auto nltag) -> hipError_t {
                 hipLaunchKernelGGL((zrun_kernel<T, M, decltype(nltag)::value>), grid, block, 0,
                                    stream, p);
+                return hipGetLastError();
+            };
+            if (n_out == 1)
+                return go(int_tag<1>{});
+            if (n_out == 2)
+                return go(int_tag<2>{});
+            return go(int_tag<3>{});
+        });
+    });
+}
+
+hipError_t
+AQZ_SHARDED(launch_zrun_tiled)(int dtype,
+                  int method,
+                  const void* src,
+                  uint64_t src_frame_elems,
+                  uint32_t W,
+                  uint32_t H,
+                  const LevelOut* outs,
+                  const TiledOut* touts,
+                  int n_out,
+                  uint32_t planes,
+                  hipStream_t stream)
+{
+    const ZRunTiledPlan pl =
+      plan_zrun_tiled(dtype, method, src, src_frame_elems, W, H, outs, touts, n_out, planes);
+    if (!pl.valid)
+        return hipErrorInvalidValue;
+    ZRunTiledParams p{};
+    p.src = static_cast<const uint8_t*>(src);
+    p.src_frame_elems = src_frame_elems;
+    p.elems = pl.elems;
+    p.spans = pl.spans;
+    p.total_units = pl.groups * pl.spans;
+    p.W = W;
+    p.dw = FastDiv::make(W);
+    for (int i = 0; i < n_out; ++i) {
+        p.dst[i] = static_cast<uint8_t*>(outs[i].ptr);
+        p.dst_frame_elems[i] = outs[i].frame_elems;
+        fill_tiled_level(p.tl[i], pl.lv[i], touts[i]);
+        if (pl.lv[i].clear_flags) {
+            // level i + 1 emits planes >> (i + 1) planes
+            const hipError_t e = hipMemsetAsync(
+              touts[i].nonzero, 0, size_t(planes >> (i + 1)) * pl.lv[i].flags_frame, stream);
+            if (e != hipSuccess)
+                return e;
+        }
+    }
+    p.zitems = pl.zitems;
+    p.zdiv = FastDiv::make(pl.zitems ? pl.zitems : 1);
+    p.zwaves = pl.zwaves;
+    const dim3 grid(pl.grid), block(pl.block);
+    return with_dtype(dtype, [&](auto tag) -> hipError_t {
+        using T = decltype(tag);
+        return with_method(method, [&](auto mtag) -> hipError_t {
+            constexpr int M = decltype(mtag)::value;
+            if (launch_log_on())
+                launch_log_record("%s", format_plan(pl).c_str());
+            auto go = [&](auto nltag) -> hipError_t {
+                hipLaunchKernelGGL((zrun_tiled_kernel<T, M, decltype(nltag)::value>), grid, block,
+                                   0, stream, p);
                 return hipGetLastError();
             };
             if (n_out == 1)

@@ -905,6 +905,100 @@ format_plan(const ZRunPlan& p)
                 static_cast<unsigned long long>(p.elems), p.grid, p.block);
 }
 
+ZRunTiledPlan
+plan_zrun_tiled(int dtype, int method, const void* src, uint64_t src_frame_elems, uint32_t W,
+                uint32_t H, const LevelOut* outs, const TiledOut* touts, int n_out,
+                uint32_t planes)
+{
+    ZRunTiledPlan p;
+    const size_t b = dtype_bytes(dtype);
+    if (!b || W == 0 || H == 0 || !outs || !touts || n_out < 1 || n_out > kMaxZLevels)
+        return p;
+    const uint64_t elems = uint64_t(W) * H;
+    // plan_zrun's rules, with a level's row-major copy optional
+    LevelOut rm[kMaxZLevels];
+    for (int i = 0; i < n_out; ++i) {
+        rm[i] = outs[i];
+        if (!rm[i].ptr) {
+            rm[i].ptr = const_cast<void*>(src);
+            rm[i].frame_elems = elems;
+        }
+    }
+    const ZRunPlan z = plan_zrun(dtype, method, src, src_frame_elems, elems, rm, n_out, planes);
+    if (!z.valid)
+        return p;
+    p.dtype = dtype;
+    p.method = method;
+    p.n_out = n_out;
+    p.bytes = z.bytes;
+    p.W = W;
+    p.H = H;
+    p.planes = planes;
+    p.groups = z.groups;
+    p.spans = z.spans;
+    p.elems = elems;
+    uint64_t zitems = 0, zbytes = 0;
+    for (int i = 0; i < n_out; ++i) {
+        const TiledOut& t = touts[i];
+        if (!t.ptr || t.tile_rows == 0 || t.tile_cols == 0 ||
+            reinterpret_cast<uintptr_t>(t.ptr) % b != 0)
+            return p;
+        TiledLevelPlan& q = p.lv[i];
+        const uint64_t ntx = (uint64_t(W) + t.tile_cols - 1) / t.tile_cols;
+        const uint64_t nty = (uint64_t(H) + t.tile_rows - 1) / t.tile_rows;
+        const uint64_t pw = ntx * t.tile_cols, ph = nty * t.tile_rows;
+        if (pw >= (1ull << 31) || ph >= (1ull << 31))
+            return p;
+        q.ntx = uint32_t(ntx);
+        q.nty = uint32_t(nty);
+        q.tframe_elems = pw * ph;
+        q.tstride = t.frame_offsets ? t.tile_stride : uint64_t(t.tile_rows) * t.tile_cols;
+        if (q.tstride < uint64_t(t.tile_rows) * t.tile_cols)
+            return p;
+        q.pw = uint32_t(pw);
+        q.ph = uint32_t(ph);
+        // the units store the frame and nothing else; the zero-fill waves take
+        // the rest of the padded area: columns past W of every padded row,
+        // else the rows past H
+        q.cov_w = W;
+        q.cov_h = H;
+        q.zrows = W < pw ? uint32_t(ph) : (H < ph ? uint32_t(ph) - H : 0u);
+        q.slots = 0;
+        q.slots_x = 1;
+        q.flags_frame = q.ntx * q.nty;
+        q.clear_flags = t.nonzero != nullptr;
+        const uint32_t per_group = 1u << (n_out - 1 - i); // the level's planes per group
+        zitems += uint64_t(q.zrows) * per_group;
+        zbytes += (pw * ph - elems) * b * per_group;
+    }
+    if (zitems * p.groups >= (1ull << 32))
+        return p;
+    p.zitems = uint32_t(zitems);
+    // zero-fill waves by plan_volume_tiled's rule: one per 128 KiB of
+    // overhang, at most 32 overhang rows per wave for 1-byte types, 64..4096
+    zbytes *= p.groups;
+    uint64_t zw = (zbytes >> 17) + 1;
+    if (b == 1)
+        zw = std::max<uint64_t>(zw, (zitems * p.groups + 31) / 32);
+    p.zwaves = zitems ? uint32_t(std::min<uint64_t>(std::max<uint64_t>(zw, 64), 4096)) : 0u;
+    p.main_blocks = z.grid;
+    // zero-fill blocks: a whole number of 8-block (one per XCD) groups
+    const uint32_t zblocks = ((p.zwaves + p.wpb - 1) / p.wpb + 7) & ~7u;
+    p.zwaves = zblocks * p.wpb;
+    p.grid = zblocks + p.main_blocks;
+    p.valid = true;
+    return p;
+}
+
+std::string
+format_plan(const ZRunTiledPlan& p)
+{
+    return line("family=zrun_tiled dtype=%u method=%d n_out=%d planes=%u groups=%u spans=%u "
+                "zitems=%u zwaves=%u grid=%u block=%u",
+                p.bytes, p.method, p.n_out, p.planes, p.groups, p.spans, p.zitems, p.zwaves,
+                p.grid, p.block);
+}
+
 int
 level_class(const PyramidLevel& in, const PyramidLevel& out)
 {

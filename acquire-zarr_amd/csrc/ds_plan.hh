@@ -293,6 +293,29 @@ struct ZRunPlan
     uint32_t grid = 0, block = 256;
 };
 
+// launch_zrun_tiled: ZRunPlan's unit geometry over planes of W x H elements
+// (elems = W * H) with one TiledLevelPlan per level of the run.  Level i + 1
+// emits planes >> (i + 1) planes, each W x H, in its own tile shape.  The
+// units' stores cover exactly the frame (cov_w = W, cov_h = H); lv[i].zrows
+// counts the zero-fill items of one emitted plane, zitems those of one plane
+// group (every level's zrows times its 2^(n_out-1-i) planes per group).  Flags
+// are one cleared byte per tile (clear_flags where the level has a flag
+// buffer).  The grid's first zwaves waves (a whole number of workgroups)
+// zero-fill; main_blocks workgroups of four units follow.
+struct ZRunTiledPlan
+{
+    bool valid = false;
+    int dtype = 0, method = 0, n_out = 0;
+    uint32_t bytes = 0;
+    // selectors: zrun_tiled_kernel<T, M, n_out>
+    uint32_t W = 0, H = 0;
+    uint32_t planes = 0, groups = 0, spans = 0;
+    uint64_t elems = 0;
+    uint32_t grid = 0, block = 256, wpb = 4;
+    uint32_t zitems = 0, zwaves = 0, main_blocks = 0;
+    TiledLevelPlan lv[kMaxZLevels];
+};
+
 // `lds_cap`: the device's LDS per workgroup, less the band kernel's static
 // arrival counter (ds_dispatch.cpp asks the device once).
 CascadePlan plan_cascade(int dtype, int method, const void* src, uint64_t src_frame_elems,
@@ -321,13 +344,26 @@ VolumeTiledPlan plan_volume_tiled(int dtype, int method, const void* src,
 ZRunPlan plan_zrun(int dtype, int method, const void* src, uint64_t src_frame_elems,
                    uint64_t elems, const LevelOut* outs, int n_out, uint32_t planes);
 
+// plan_zrun over planes of W x H elements, every level also (outs[i].ptr
+// null: only) written as chunk tiles.  outs[i].ptr may be null; where it is
+// set, plan_zrun's rules hold for it.  touts[i].frame_offsets, when set, holds
+// planes >> (i + 1) entries.  Invalid on top of plan_zrun's rules: W or H
+// zero, a null, misaligned or zero-shaped tile output, a tile stride below one
+// tile, a padded side or the unit count at 2^31 or more, zero-fill items at
+// 2^32 or more (plan_volume_tiled's limits).  A Z level has no width rule.
+ZRunTiledPlan plan_zrun_tiled(int dtype, int method, const void* src, uint64_t src_frame_elems,
+                              uint32_t W, uint32_t H, const LevelOut* outs,
+                              const TiledOut* touts, int n_out, uint32_t planes);
+
 // The launch log's line (launch_log.hh) for a valid plan: family=cascade or
-// family=band, family=tiled, family=volume, family=volume_tiled, family=zrun.
+// family=band, family=tiled, family=volume, family=volume_tiled, family=zrun,
+// family=zrun_tiled.
 std::string format_plan(const CascadePlan& p);
 std::string format_plan(const TiledPlan& p);
 std::string format_plan(const VolumePlan& p);
 std::string format_plan(const VolumeTiledPlan& p);
 std::string format_plan(const ZRunPlan& p);
+std::string format_plan(const ZRunTiledPlan& p);
 
 // ---- pyramids as runs ---------------------------------------------------------
 // What a level (l >= 1) does to the one before it: halve XY and Z, XY alone,

@@ -1874,11 +1874,11 @@ namespace {
 
 // Per-level frame offsets of a chunk-lattice batch into the device (elements),
 // through one half of the pinned staging; returns the device pointers.
-// `halving`: level l carries n_frames >> l offsets (a volume batch), not
-// n_frames.
+// `counts`, when set: level l carries counts[l] <= n_frames offsets (a volume
+// or mixed batch, whose Z-halving levels emit fewer frames), not n_frames.
 int
 stage_lattice(aqz_ds* ds, const aqz_chunk_lattice* lat, uint32_t n_frames, hipStream_t stream,
-              std::vector<const uint64_t*>* dev, int* half_out, bool halving = false,
+              std::vector<const uint64_t*>* dev, int* half_out, const uint32_t* counts = nullptr,
               bool base = false)
 {
     // `base`: slot 0 (level 0's offsets) is staged too
@@ -1904,7 +1904,7 @@ stage_lattice(aqz_ds* ds, const aqz_chunk_lattice* lat, uint32_t n_frames, hipSt
     uint64_t* d = static_cast<uint64_t*>(ds->d_lattice.get()) + size_t(half) * lattice_half;
     dev->assign(ds->n, nullptr);
     for (uint32_t l = l0; l < ds->n; ++l)
-        for (uint32_t k = 0, nk = halving ? n_frames >> l : n_frames; k < nk; ++k)
+        for (uint32_t k = 0, nk = counts ? counts[l] : n_frames; k < nk; ++k)
             h[size_t(l) * n_frames + k] = lat[l].frame_offset_bytes[k] / ds->bpp;
     HIP_TRY(ds, hipMemcpyAsync(d, h, need * 8, hipMemcpyHostToDevice, stream), "lattice upload");
     for (uint32_t l = l0; l < ds->n; ++l)
@@ -2035,7 +2035,7 @@ run_tiled(aqz_ds* ds,
     std::vector<const uint64_t*> d_off;
     int half = -1;
     if (lat)
-        if (int rc = stage_lattice(ds, lat, n_frames, stream, &d_off, &half, false, base))
+        if (int rc = stage_lattice(ds, lat, n_frames, stream, &d_off, &half, nullptr, base))
             return rc;
     // From here on the staged half's upload is queued on `stream`: whatever
     // the exit, record the event that guards the pinned half, so a later call
@@ -2253,9 +2253,13 @@ run_volume_tiled(aqz_ds* ds,
     hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ds->stream;
     std::vector<const uint64_t*> d_off;
     int half = -1;
-    if (lat)
-        if (int rc = stage_lattice(ds, lat, n_frames, stream, &d_off, &half, true))
+    if (lat) {
+        std::vector<uint32_t> per_level(ds->n);
+        for (uint32_t l = 0; l < ds->n; ++l)
+            per_level[l] = n_frames >> l;
+        if (int rc = stage_lattice(ds, lat, n_frames, stream, &d_off, &half, per_level.data()))
             return rc;
+    }
     // as in run_tiled: the staged half's event on every way out
     struct LatticeGuard
     {
@@ -2325,6 +2329,245 @@ run_volume_tiled(aqz_ds* ds,
             out_counts[l] = n_frames >> l;
     }
     ds->last_batch_kind = 5;
+    return AQZ_OK;
+}
+
+// The handle's pyramid as plan_pyramid_runs reads it.
+std::vector<aqz::PyramidLevel>
+pyramid_levels(const aqz_ds* ds)
+{
+    std::vector<aqz::PyramidLevel> pl(ds->n);
+    for (uint32_t l = 0; l < ds->n; ++l) {
+        const Level& lv = ds->lv[l];
+        pl[l] = { lv.desc.width, lv.desc.height, lv.desc.planes, l > 0 && lv.has_partial };
+    }
+    return pl;
+}
+
+// aqz_ds_run_device_mixed_tiled (lat == nullptr) and
+// aqz_ds_run_device_mixed_chunked: run_tiled's two forms for the pyramids
+// aqz_ds_run_device_batch runs as kind 7 — plan_pyramid_runs' runs, each
+// through its tiled launcher (launch_volume_tiled, launch_cascade_tiled,
+// launch_zrun_tiled), chained through d_chain.  Level l emits
+// n_frames >> zcount(l) frames.  All or nothing: every run is planned before
+// anything is queued, and there is no per-frame form to fall back to.
+int
+run_mixed_tiled(aqz_ds* ds,
+                const char* who,
+                const void* device_frames,
+                uint32_t n_frames,
+                const uint32_t* tile_rows,
+                const uint32_t* tile_cols,
+                void* const* device_out_levels,
+                const aqz_chunk_lattice* lat,
+                uint8_t* const* device_tile_nonzero,
+                uint32_t* out_counts,
+                void* hip_stream)
+{
+    const std::string w(who);
+    if (int rc = settle(ds))
+        return rc;
+    if (ds->transpose)
+        return ds->fail_arg(w + ": input transposition applies to the per-frame path only");
+    ds->last_input = nullptr;
+    if (!device_frames || (!lat && (!device_out_levels || !tile_rows || !tile_cols)))
+        return ds->fail_arg(w + ": null argument");
+    if (ds->n < 2)
+        return ds->fail_arg(w + ": the pyramid has no level to tile");
+    const std::vector<aqz::PyramidLevel> pl = pyramid_levels(ds);
+    const aqz::PyramidRuns mixed = aqz::plan_pyramid_runs(pl.data(), ds->n, n_frames);
+    if (!mixed.ok)
+        return ds->fail_arg(w + ": " + mixed.reason);
+    // frames each level emits: n_frames >> zcount(l)
+    std::vector<uint32_t> emits(ds->n);
+    for (uint32_t l = 0, frames = n_frames; l < ds->n; ++l) {
+        if (l > 0 && pl[l].planes < pl[l - 1].planes)
+            frames >>= 1;
+        emits[l] = frames;
+    }
+    for (uint32_t l = 1; l < ds->n; ++l) {
+        const uint32_t tr = lat ? lat[l].tile_rows : tile_rows[l];
+        const uint32_t tc = lat ? lat[l].tile_cols : tile_cols[l];
+        const void* out = lat ? lat[l].device_base : device_out_levels[l];
+        if (!out || !tr || !tc)
+            return ds->fail_arg(w + ": level " + std::to_string(l) +
+                                " needs an output and a nonzero tile shape");
+        if (lat) {
+            // run_tiled's lattice checks over the level's own frame count
+            const aqz_chunk_lattice& c = lat[l];
+            const uint64_t ntiles = uint64_t((ds->lv[l].desc.width + tc - 1) / tc) *
+                                    ((ds->lv[l].desc.height + tr - 1) / tr);
+            const uint64_t tile_bytes = uint64_t(tr) * tc * ds->bpp;
+            if (!c.frame_offset_bytes || c.chunk_stride_bytes % ds->bpp ||
+                c.chunk_stride_bytes < tile_bytes)
+                return ds->fail_arg(w + ": level " + std::to_string(l) +
+                                    ": chunk stride must hold a tile and be a multiple of the "
+                                    "pixel size, and frame offsets are required");
+            const uint64_t extent = (ntiles - 1) * c.chunk_stride_bytes + tile_bytes;
+            for (uint32_t k = 0; k < emits[l]; ++k) {
+                const uint64_t off = c.frame_offset_bytes[k];
+                if (off % ds->bpp || off > c.capacity_bytes || c.capacity_bytes - off < extent)
+                    return ds->fail_arg(w + ": level " + std::to_string(l) + " frame " +
+                                        std::to_string(k) + ": offset " + std::to_string(off) +
+                                        " puts its tiles outside the lattice buffer");
+            }
+        }
+    }
+    const auto tiled_outs = [&](uint32_t L, uint32_t k, const std::vector<const uint64_t*>& off,
+                                aqz::TiledOut* t) {
+        for (uint32_t j = 0; j < k; ++j) {
+            const uint32_t l = L + j;
+            uint8_t* nz = device_tile_nonzero ? device_tile_nonzero[l] : nullptr;
+            if (lat)
+                t[j] = { lat[l].device_base, lat[l].tile_rows, lat[l].tile_cols, nz,
+                         off.empty() ? lat[l].frame_offset_bytes : off[l],
+                         lat[l].chunk_stride_bytes / ds->bpp };
+            else
+                t[j] = { device_out_levels[l], tile_rows[l], tile_cols[l], nz };
+        }
+    };
+    // One run through its tiled launcher, or (`queue` false) its plan alone.
+    // The plans look at addresses and sizes only, so a stand-in for the chain
+    // scratch (aligned, like the allocation) and the offsets' host copy serve
+    // there.
+    const size_t n_runs = mixed.runs.size();
+    const auto do_run = [&](size_t i, const void* src, void* feed,
+                            const std::vector<const uint64_t*>& off, bool queue,
+                            hipStream_t stream, std::string* why) -> hipError_t {
+        const aqz::PyramidRun& r = mixed.runs[i];
+        const int k = int(r.levels);
+        aqz::LevelOut o[aqz::kMaxFusedLevels];
+        aqz::TiledOut t[aqz::kMaxFusedLevels];
+        fill_outs(ds, r.first, r.levels, [](uint32_t) { return nullptr; }, o);
+        tiled_outs(r.first, r.levels, off, t);
+        if (i + 1 < n_runs)
+            o[k - 1].ptr = feed;
+        const Level& a = ds->lv[r.first - 1];
+        const uint32_t W = a.desc.width, H = a.desc.height;
+        const std::string levels = "levels " + std::to_string(r.first) + ".." +
+                                   std::to_string(r.first + r.levels - 1);
+        const char* limits = ": misaligned output, or units, padded sides or zero-fill items "
+                             "past the launch limits";
+        if (r.cls == aqz::kClassXYZ) {
+            if (queue)
+                return aqz::launch_volume_tiled(ds->dtype, ds->method, src, a.elems(), W, H, o, t,
+                                                k, r.frames_in, stream);
+            if (!aqz::volume_supported(ds->dtype, src, W, H, o, k))
+                *why = "level " + std::to_string(r.first - 1) +
+                       " does not fit the fused volume kernel (" + std::to_string(W) +
+                       " px wide: narrower than one vector load, or a misaligned buffer)";
+            else if (!aqz::plan_volume_tiled(ds->dtype, ds->method, src, a.elems(), W, H, o, t, k,
+                                             r.frames_in, aqz::launch_switches())
+                        .valid)
+                *why = levels + limits;
+        } else if (r.cls == aqz::kClassXY) {
+            if (queue)
+                return aqz::launch_cascade_tiled(ds->dtype, ds->method, src, a.elems(), W, H, o, t,
+                                                 k, r.frames_in, stream);
+            if (!aqz::cascade_supported(ds->dtype, src, a.elems(), W, H, o, k))
+                *why = "level " + std::to_string(r.first - 1) +
+                       " is narrower than one vector load (" + std::to_string(W) +
+                       " px) or misaligned";
+            else if (!aqz::plan_cascade_tiled(ds->dtype, ds->method, src, a.elems(), W, H, o, t, k,
+                                              r.frames_in, aqz::launch_switches())
+                        .valid)
+                *why = levels + limits;
+        } else {
+            if (queue)
+                return aqz::launch_zrun_tiled(ds->dtype, ds->method, src, a.elems(), W, H, o, t, k,
+                                              r.frames_in, stream);
+            bool same = true;
+            for (int j = 0; j < k; ++j)
+                same = same && o[j].w == W && o[j].h == H;
+            if (!same)
+                *why = levels + " do not keep level " + std::to_string(r.first - 1) + "'s size";
+            else if (!aqz::plan_zrun_tiled(ds->dtype, ds->method, src, a.elems(), W, H, o, t, k,
+                                           r.frames_in)
+                        .valid)
+                *why = levels + limits;
+        }
+        return hipSuccess;
+    };
+    {
+        void* const stand_in = reinterpret_cast<void*>(uintptr_t(256));
+        const std::vector<const uint64_t*> none;
+        for (size_t i = 0; i < n_runs; ++i) {
+            std::string why;
+            (void)do_run(i, i == 0 ? device_frames : stand_in, stand_in, none, false, nullptr,
+                         &why);
+            if (!why.empty())
+                return ds->fail_arg(w + ": " + why);
+        }
+    }
+    if (int rc = bind_device(ds))
+        return rc;
+    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ds->stream;
+    std::vector<const uint64_t*> d_off;
+    int half = -1;
+    if (lat)
+        if (int rc = stage_lattice(ds, lat, n_frames, stream, &d_off, &half, emits.data()))
+            return rc;
+    // as in run_tiled: the staged half's event on every way out
+    struct LatticeGuard
+    {
+        aqz_ds* ds;
+        int half;
+        hipStream_t stream;
+        ~LatticeGuard()
+        {
+            if (half >= 0)
+                (void)hipEventRecord(ds->lattice_done[half], stream);
+        }
+    } lattice_guard{ ds, half, stream };
+    // A run that feeds another also writes its last level row-major into one
+    // half of d_chain (alternating by run parity), ordered behind the handle's
+    // previous deep batch by chain_done — run_tiled's scheme.  A half holds
+    // the largest level a run feeds.
+    const bool chained = n_runs > 1;
+    if (chained) {
+        if (ds->chain_done)
+            HIP_TRY(ds, hipStreamWaitEvent(stream, ds->chain_done, 0), "hipStreamWaitEvent chain");
+        else
+            HIP_TRY(ds, ds->chain_done.create(), "event");
+    }
+    struct ChainGuard
+    {
+        aqz_ds* ds;
+        hipStream_t stream;
+        bool on;
+        ~ChainGuard()
+        {
+            if (on)
+                (void)hipEventRecord(ds->chain_done, stream);
+        }
+    } chain_guard{ ds, stream, chained };
+    if (chained) {
+        size_t chain_half = 0;
+        for (size_t i = 0; i + 1 < n_runs; ++i) {
+            const uint32_t last = mixed.runs[i].first + mixed.runs[i].levels - 1;
+            chain_half = std::max(chain_half, size_t(emits[last]) * ds->lv[last].bytes);
+        }
+        chain_half = (chain_half + 255) & ~size_t(255);
+        if (ds->d_chain.capacity() < 2 * chain_half) {
+            HIP_TRY(ds, hipStreamSynchronize(stream), "hipStreamSynchronize");
+            HIP_TRY(ds, ds->d_chain.reserve(2 * chain_half), "hipMalloc chain");
+        }
+    }
+    const void* src = device_frames;
+    for (size_t i = 0; i < n_runs; ++i) {
+        void* chain = ds->d_chain.bytes() + (i & 1) * (ds->d_chain.capacity() / 2);
+        const hipError_t e = do_run(i, src, chain, d_off, true, stream, nullptr);
+        if (e != hipSuccess)
+            return e == hipErrorInvalidValue ? ds->fail_arg(w + ": unsupported geometry")
+                                             : ds->fail(e, "batch tiled mixed runs");
+        src = chain;
+    }
+    for (uint32_t l = 0; l < ds->n; ++l) {
+        ds->lv[l].count += emits[l];
+        if (out_counts)
+            out_counts[l] = emits[l];
+    }
+    ds->last_batch_kind = 8;
     return AQZ_OK;
 }
 
@@ -2487,6 +2730,85 @@ aqz_ds_tiled_flag_slots(const aqz_ds* ds, uint32_t level, uint32_t tile_rows, ui
                                                 int(level - start + 1), tile_rows, tile_cols,
                                                 nullptr);
     return s ? s : 1;
+}
+
+int
+aqz_ds_run_device_mixed_tiled(aqz_ds* ds,
+                              const void* device_frames,
+                              uint32_t n_frames,
+                              const uint32_t* tile_rows,
+                              const uint32_t* tile_cols,
+                              void* const* device_out_levels,
+                              uint8_t* const* device_tile_nonzero,
+                              uint32_t* out_counts,
+                              void* hip_stream)
+{
+    try {
+        if (!ds)
+            return AQZ_INVALID_ARGUMENT;
+        return run_mixed_tiled(ds, "run_device_mixed_tiled", device_frames, n_frames, tile_rows,
+                               tile_cols, device_out_levels, nullptr, device_tile_nonzero,
+                               out_counts, hip_stream);
+    } catch (...) {
+        return ABI_GUARD_FAIL(ds);
+    }
+}
+
+int
+aqz_ds_run_device_mixed_chunked(aqz_ds* ds,
+                                const void* device_frames,
+                                uint32_t n_frames,
+                                const aqz_chunk_lattice* lattices,
+                                uint8_t* const* device_tile_nonzero,
+                                uint32_t* out_counts,
+                                void* hip_stream)
+{
+    try {
+        if (!ds)
+            return AQZ_INVALID_ARGUMENT;
+        if (!lattices)
+            return ds->fail_arg("run_device_mixed_chunked: null lattices");
+        return run_mixed_tiled(ds, "run_device_mixed_chunked", device_frames, n_frames, nullptr,
+                               nullptr, nullptr, lattices, device_tile_nonzero, out_counts,
+                               hip_stream);
+    } catch (...) {
+        return ABI_GUARD_FAIL(ds);
+    }
+}
+
+uint32_t
+aqz_ds_mixed_flag_slots(const aqz_ds* ds, uint32_t level, uint32_t tile_rows, uint32_t tile_cols)
+{
+    try {
+        if (!ds || level == 0 || level >= ds->n || tile_rows == 0 || tile_cols == 0)
+            return 0;
+        // the run cut does not depend on the batch: any accepted frame count
+        // gives it, and a plane some level holds now is the call's to refuse
+        std::vector<aqz::PyramidLevel> pl = pyramid_levels(ds);
+        uint32_t zcount = 0;
+        for (uint32_t l = 1; l < ds->n; ++l) {
+            pl[l].holds_plane = false;
+            zcount += pl[l].planes < pl[l - 1].planes ? 1 : 0;
+        }
+        if (zcount >= 32)
+            return 0;
+        const aqz::PyramidRuns mixed = aqz::plan_pyramid_runs(pl.data(), ds->n, 1u << zcount);
+        if (!mixed.ok)
+            return 0;
+        for (const aqz::PyramidRun& r : mixed.runs) {
+            if (level < r.first || level >= r.first + r.levels)
+                continue;
+            if (r.cls != aqz::kClassXY)
+                return 1;
+            const uint32_t s =
+              aqz::cascade_tiled_slots(ds->dtype, ds->lv[r.first - 1].desc.width, int(r.levels),
+                                       int(level - r.first + 1), tile_rows, tile_cols, nullptr);
+            return s ? s : 1;
+        }
+        return 0;
+    } catch (...) {
+        return 0;
+    }
 }
 
 namespace {

@@ -641,6 +641,78 @@ int aqz_ds_run_device_volume_chunked(aqz_ds* ds,
                                      void* hip_stream);
 
 /*
+ * aqz_ds_run_device_batch_tiled / _chunked for mixed 3-D pyramids: some levels
+ * halve X, Y and Z, others XY alone or Z alone, in any order — what the
+ * level planner makes for most 3-D acquisitions (XYZ levels, then an XY-only
+ * or a Z-only tail).  The results are those of aqz_ds_run_device_batch on the
+ * same handle and frames when it takes the chain of batched runs
+ * (aqz_ds_last_batch_kind 7): level L emits n_frames >> zcount(L) frames,
+ * zcount(L) the Z-halving levels among 1..L; `out_counts` reports that and the
+ * handle's per-level counts advance the same way.  The k-th emitted frame of
+ * level L is written in the tile layout aqz_ds_run_device_batch_tiled
+ * documents — frames back to back in `device_out_levels[L]`, or, for the
+ * chunked form, tile t at lattices[L].frame_offset_bytes[k] + t *
+ * chunk_stride_bytes, where frame_offset_bytes has n_frames >> zcount(L)
+ * entries (aqz_chunk_frame_offsets on level L's own dimensions).  Index 0 of
+ * every array is ignored.  The pyramid is cut into runs of one class — up to
+ * 2 XYZ levels, 4 XY levels, 3 Z levels — and each run is one fused kernel
+ * writing its levels as tiles from registers (the tiled volume kernel, the
+ * tiled cascade, the tiled Z run), its first waves zeroing the tile overhang;
+ * no row-major pass, no tiling pass.
+ * `device_tile_nonzero[L]` (optional) receives
+ * aqz_ds_mixed_flag_slots(ds, L, tile_rows[L], tile_cols[L]) flag bytes per
+ * tile per emitted frame: 1 on XYZ and Z levels (cleared by a fill queued
+ * ahead of the kernel, set to 1 by the lanes that store a nonzero byte), and
+ * on XY levels the tiled cascade's count for the level's place in its own run
+ * (not aqz_ds_tiled_flag_slots' fixed cut into levels 1-4, 5-8, ...); a tile
+ * holds data iff any of its bytes is nonzero — the layout
+ * aqz_zarr_shard_chunk_has_data_device takes.  aqz_ds_mixed_flag_slots
+ * returns 0 for a bad level or tile shape, or a pyramid with a level that
+ * halves neither XY nor Z or pairs an odd plane count.
+ * Accepted when every level has a class, every Z-halving level has an even
+ * plane count in front of it and holds no earlier plane of the per-frame
+ * path, `n_frames` is a nonzero multiple of 2^zcount(last), every level >= 1
+ * has an output and a nonzero tile shape, no input transposition is set, and
+ * every run fits its fused kernel: an XYZ or XY run starts at a level no
+ * narrower than one vector load; a Z run takes any size.  Pure-XY and pure-XYZ pyramids
+ * are accepted too (one class of runs).  Anything else — an odd stack, a
+ * lattice that fails aqz_ds_run_device_batch_chunked's checks over each
+ * level's own frame count, a launch past its limits — is AQZ_INVALID_ARGUMENT
+ * with a message naming the level; every run is planned before anything is
+ * queued, nothing is written, and there is no fallback path (the row-major
+ * call keeps its per-frame path for such pyramids).  The 2-D and volume
+ * tiled calls keep refusing mixed pyramids.
+ * Stream rules as for those calls: everything is queued on `hip_stream`
+ * (NULL = the handle's stream) and the call does not wait on the host, except
+ * the call that grows scratch.  Pyramids of more than one run chain them
+ * through the same handle scratch, ordered behind the handle's previous deep
+ * batch by an event wait; the chunked form stages its offsets through the
+ * same two pinned halves (a third call in flight waits for the first).
+ */
+int aqz_ds_run_device_mixed_tiled(aqz_ds* ds,
+                                  const void* device_frames,
+                                  uint32_t n_frames,
+                                  const uint32_t* tile_rows,
+                                  const uint32_t* tile_cols,
+                                  void* const* device_out_levels,
+                                  uint8_t* const* device_tile_nonzero,
+                                  uint32_t* out_counts,
+                                  void* hip_stream);
+
+int aqz_ds_run_device_mixed_chunked(aqz_ds* ds,
+                                    const void* device_frames,
+                                    uint32_t n_frames,
+                                    const aqz_chunk_lattice* lattices,
+                                    uint8_t* const* device_tile_nonzero,
+                                    uint32_t* out_counts,
+                                    void* hip_stream);
+
+uint32_t aqz_ds_mixed_flag_slots(const aqz_ds* ds,
+                                 uint32_t level,
+                                 uint32_t tile_rows,
+                                 uint32_t tile_cols);
+
+/*
  * Where frames first_frame .. first_frame + n_frames - 1 of an array with
  * storage-order dimensions `dims` (ndims >= 3, the last two Y and X) put
  * their tile 0 in a lattice of chunk buffers `*chunk_bytes` apart:
@@ -679,8 +751,9 @@ int aqz_ds_run_host_batch(aqz_ds* ds,
                           uint32_t* out_counts);
 
 /*
- * Diagnostic: the path the last aqz_ds_run_device_batch[_tiled] or
- * aqz_ds_run_device_volume_tiled / _chunked took —
+ * Diagnostic: the path the last aqz_ds_run_device_batch[_tiled],
+ * aqz_ds_run_device_volume_tiled / _chunked or
+ * aqz_ds_run_device_mixed_tiled / _chunked took —
  * 0 = per-frame state machine, 1 = fused 2-D cascade, 2 = fused volume
  * (XY + Z), 3 = 2-D batch with some level runs on batched single-level
  * kernels (frames narrower than one 16-byte load, or buffers that are not
@@ -691,6 +764,8 @@ int aqz_ds_run_host_batch(aqz_ds* ds,
  * (aqz_ds_run_device_batch_tiled_base / _chunked_base),
  * 7 = mixed pyramid as a chain of batched runs (fused volume, fused cascade
  * or batched single-level XY kernels, Z run; aqz_ds_run_device_batch),
+ * 8 = mixed pyramid as a chain of fused runs writing chunk tiles
+ * (aqz_ds_run_device_mixed_tiled / _chunked),
  * -1 = none.
  */
 int aqz_ds_last_batch_kind(const aqz_ds* ds);
